@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the batched flight_easy / flight environment path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--mode step|rollout]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--mode step|rollout] [--full]
+                    [--dump-outputs DIR]
 
 One "step" = one env.step() of EVERY environment of the batch, including the obs + state emission that
 common/rollout.py:45-63 needs each step.  Inputs (pre-drawn uniform actions) are resident in HBM before the
@@ -21,10 +22,23 @@ Modes:
              the kinematics / detection of step t + 1 run side by side (k_flight_pipe)
 
 Timing protocol (one clock): after W warm-up steps, the K-step region -- bracketed by a barrier and
-torch.cuda.synchronize() on both sides -- is repeated until it has accumulated >= MIN_GPU_S of GPU time (at least
-5 times); each repeat is timed with HIP events recorded on the stream the kernels are launched on (torch's current
-stream).  `value`, `ms_per_step` and `roofline.achieved` all derive from the MEDIAN event interval of the K-step
-region (max over ranks); the host wall clock of the same repeats is reported next to it as `wall_ms_per_step`.
+torch.cuda.synchronize() on both sides -- is timed ONCE with HIP events recorded on the stream the kernels are launched
+on (torch's current stream), so K is the number of timed steps.  `value`, `ms_per_step` and `roofline.achieved` all
+derive from that event interval (max over ranks); the host wall clock of the same region is reported next to it as
+`wall_ms_per_step`.  A region that follows a short warm-up reads low (c2, 2000 steps on MI355X: 3.38e9 env-steps/s after
+200 warm-up steps, 3.54e9 after 20 000, 3.56e9 as the median of many repeats), so short runs want a long --warmup.
+
+A plain run does only what the headline needs.  `--full` adds everything else, each as before: the K-step region is
+repeated until it has accumulated >= --min-gpu-s of GPU time (at least 5 times) and the figures derive from the MEDIAN
+repeat; the secondary workloads (`also`, at N > 1 only the two c5 points unless --also); the CPU baseline
+(--no-cpu-baseline and --no-also switch those two off again); at N = 1 the optional one-rank RCCL group (--pg auto) and the
+timing of the metric all-gather; and the full record in a detail file next to the line.
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path computed in its last step (rank 0's shard): the
+arrays a caller receives (reward, terminated, win, obs, state) as DIR/<name>.npy in float32, taken after the first timed
+region, so that a plain and a --full run with the same arguments dump the same values.  Inputs (env seeds, actions) are
+fixed by the arguments.  When all envs would exceed DUMP_MAX_BYTES, one fixed, seeded sample of envs is written for every
+array; DIR/env_index.npy (float64) names the envs written.
 
 Multi-GPU: `--gpus N` with no torchrun environment starts N fresh rank processes itself (python -m
 torch.distributed.run, one rank per GPU, backend nccl = RCCL) BEFORE anything touches the GPU, relays rank 0's JSON
@@ -60,6 +74,8 @@ MIN_GPU_S = 1.0          # headline: repeat the K-step region until this much GP
 MIN_GPU_S_ALSO = 0.25    # secondary workloads
 MIN_REPEATS, MAX_REPEATS = 5, 20000
 PG_WATCHDOG_S = 120      # --pg auto at N = 1: how long the optional RCCL communicator may take to come up
+DUMP_MAX_BYTES = 60_000_000   # --dump-outputs: all arrays together, .npy headers aside (the ceiling is 64 MB)
+DUMP_SAMPLE_SEED = 0          # --dump-outputs: the env sample taken when the whole batch does not fit
 
 
 def parse_args(argv=None):
@@ -70,22 +86,30 @@ def parse_args(argv=None):
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     ap.add_argument("--mode", default=None, choices=["step", "rollout"])
     ap.add_argument("--batch", type=int, default=None, help="override envs per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline: repeats of the K-step region up to --min-gpu-s, the secondary "
+                         "workloads ('also'), the CPU baseline, at N = 1 the optional RCCL group and the all-gather timing, "
+                         "and the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0's shard) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary workloads reported under 'also'")
+    ap.add_argument("--no-also", action="store_true", help="--full without the secondary workloads reported under 'also'")
     ap.add_argument("--also", action="store_true",
-                    help="N > 1: run the whole list of secondary workloads on every rank too (default at N > 1: the headline and "
-                         "the two c5 lines only, so that a scaling run is not 8x longer than it has to be)")
+                    help="--full at N > 1: run the whole list of secondary workloads on every rank too (default at N > 1: the "
+                         "headline and the two c5 lines only, so that a scaling run is not 8x longer than it has to be)")
     ap.add_argument("--kernel", default="auto", choices=["auto", "group", "od", "ode", "oct", "lane", "lanev"],
                     help="flight_easy kernel: 16 lanes per env (group: a rollout is T launches of the step kernel), 8 lanes per env "
                          "(od: kinematics + detection wavefront pair, oct: one wavefront), one lane per env, or everything by "
                          "batch size (auto: ode up to 8192 envs, od up to 16384, oct below 65536 -- teams of 6 to 8: below 2^20 --, lanev from 65536 "
                          "for teams of up to 5, lane from 2^20 for larger ones; DESIGN.md section 4)")
-    ap.add_argument("--min-gpu-s", type=float, default=MIN_GPU_S)
-    ap.add_argument("--pg", default="auto", choices=["auto", "on", "off"],
+    ap.add_argument("--min-gpu-s", type=float, default=MIN_GPU_S,
+                    help="--full: repeat the K-step region until this much GPU time has been measured")
+    ap.add_argument("--pg", default=None, choices=["auto", "on", "off"],
                     help="process group at N = 1: 'on' = init_process_group('nccl') even for one rank and fail if RCCL does "
-                         "not come up; 'auto' (default) = try it, report the failure in the line and carry on without "
-                         "(the collective is outside the timed region); 'off' = none.  N > 1 always has one.")
+                         "not come up; 'auto' (default with --full) = try it, report the failure in the line and carry on "
+                         "without (the collective is outside the timed region); 'off' (default otherwise) = none.  N > 1 "
+                         "always has one.")
     ap.add_argument("--force-pg", dest="pg", action="store_const", const="on", help="same as --pg on")
     ap.add_argument("--cpu-baseline-child", default=None, help=argparse.SUPPRESS)   # "env,n,batch,budget": see cpu_baseline()
     ap.add_argument("--no-numa-bind", action="store_true",
@@ -93,7 +117,10 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU-only check of the N-rank control flow (launcher, gloo process group, metric all-gather); "
                          "no kernels run and the line says so")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.pg is None:
+        a.pg = "auto" if a.full else "off"
+    return a
 
 
 # ---------------------------------------------------------------------------------------------- the one stdout line
@@ -635,9 +662,10 @@ def time_metric_allgather(dist, cdev, reps=100, torch=None, sync=None):
             "clock": "host wall time around all_gather + device synchronisation"}
 
 
-def timed_region(region, dev, comm, min_gpu_s):
+def timed_region(region, dev, comm, min_gpu_s, after_first=None):
     """Repeats `region()` (the K-step region) bracketed by barrier + synchronize on both sides; returns the per-repeat
-    HIP-event seconds and host wall seconds.  Every rank runs the same number of repeats."""
+    HIP-event seconds and host wall seconds.  Every rank runs the same number of repeats.  min_gpu_s None: one repeat.
+    `after_first()` runs once the first repeat has finished on the device, outside the timed interval."""
     import torch
 
     def once():
@@ -656,6 +684,10 @@ def timed_region(region, dev, comm, min_gpu_s):
         return ev0.elapsed_time(ev1) / 1e3, wall
 
     first = once()
+    if after_first is not None:
+        after_first()
+    if min_gpu_s is None:
+        return [first[0]], [first[1]]
     reps = int(min(MAX_REPEATS, max(MIN_REPEATS, math.ceil(min_gpu_s / max(comm.max(first[0]), 1e-7)))))
     ev, wall = [first[0]], [first[1]]
     for _ in range(reps - 1):
@@ -665,10 +697,35 @@ def timed_region(region, dev, comm, min_gpu_s):
     return ev, wall
 
 
-def run_workload(cs, dev, comm, env_name, n, B, mode, K, W, kernel, rank=0, no_graph=False, min_gpu_s=MIN_GPU_S_ALSO):
-    """Measures K steps of one workload on every rank; returns (result dict, env).  Times are max over ranks."""
+def output_sample(last, B):
+    """The last step's outputs {name: [B, ...] device tensor} as float32 host arrays: every env while they fit in
+    DUMP_MAX_BYTES, otherwise one fixed, seeded sample of envs for every array.  `env_index` (float64) names the envs."""
+    import numpy as np
+    import torch
+    per_env = sum(t[0].numel() for t in last.values()) * 4 + 8
+    k = min(B, DUMP_MAX_BYTES // per_env)
+    idx = np.arange(B) if k == B else np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(B, k, replace=False))
+    sel = torch.from_numpy(idx).to(next(iter(last.values())).device)
+    arrays = {name: t.index_select(0, sel).float().cpu().numpy() for name, t in last.items()}
+    arrays["env_index"] = idx.astype(np.float64)
+    return arrays
+
+
+def write_outputs(arrays, path):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
+def run_workload(cs, dev, comm, env_name, n, B, mode, K, W, kernel, rank=0, no_graph=False, min_gpu_s=MIN_GPU_S_ALSO,
+                 dump=False):
+    """Measures K steps of one workload on every rank; returns (result dict, env, outputs).  Times are max over ranks.
+    min_gpu_s None: the K steps are timed once.  outputs: output_sample() of the last step of the first timed region when
+    `dump`, else None."""
     import torch
     m = 15
+    last = {}   # the arrays a caller receives from the last step run, as device tensors the next steps overwrite
     S = largest_divisor_leq(K, 100)  # steps per graph replay / per rollout launch
     env = cs.BatchedFlightEnv(cs.make_env_args(env_name, n_agents=n), batch=B, device=dev, env_offset=rank * B,
                               freeze_done=False, auto_reset=True, kernel=kernel)
@@ -681,13 +738,15 @@ def run_workload(cs, dev, comm, env_name, n, B, mode, K, W, kernel, rank=0, no_g
             win=torch.empty(S, B, dtype=torch.uint8, device=dev),
             obs=torch.empty(S, B, n, env.obs_width, dtype=torch.float32, device=dev),
             state=torch.empty(S, B, env.state_shape, dtype=torch.float32, device=dev))
+        last.update((k, v[-1]) for k, v in out.items())
 
         def chunk_eager():
             env.rollout(acts, out=out, update_views=False)
     else:
         def chunk_eager():
-            for s in range(S):
-                env.step(acts[s])
+            for s in range(S):   # (under graph capture: the env's own output buffers, which every replay rewrites)
+                last["reward"], last["terminated"], last["win"] = env.step(acts[s])
+            last["obs"], last["state"] = env.get_obs(), env.get_state()
     if no_graph or mode == "rollout":
         # rollout mode: one cs_rollout call per chunk, launched directly.  (Replaying it from a hipGraph was measured: the
         # graph launch costs MORE than the plain launch it replaces -- 58.7 against 52.2 us per 20-step region at c2.)
@@ -713,7 +772,12 @@ def run_workload(cs, dev, comm, env_name, n, B, mode, K, W, kernel, rank=0, no_g
         for _ in range(K // S):
             chunk()
 
-    ev, wall = timed_region(region, dev, comm, min_gpu_s)
+    outputs = {}
+
+    def snapshot():
+        outputs.update(output_sample(last, B))
+
+    ev, wall = timed_region(region, dev, comm, min_gpu_s, after_first=snapshot if dump else None)
     t_ev = comm.max(statistics.median(ev))
     t_wall = comm.max(statistics.median(wall))
     # every rank's own rate (its median region), not only the slowest one's: a straggler shows as min << median
@@ -743,14 +807,14 @@ def run_workload(cs, dev, comm, env_name, n, B, mode, K, W, kernel, rank=0, no_g
                      "context": "peak = HBM3E spec; measured on MI355X (tools/probe_write_bw.hip, profiles/r06_write_bw.log): read 6.2-6.4, "
                                 "copy 4.6-5.4, pure write 4.1-5.4 TB/s; this path writes >= 90 % of its bytes"},
     }
-    return res, env
+    return res, env, (outputs if dump else None)
 
 
 def side_measurement(cs, dev, comm, key, label, env_name, n, B, mode, K, W, kernel, rank=0):
     """Entry for the `also` list (detail file; `key` names it in the line's also_summary): another workload measured in the
     same run with the same protocol."""
     import torch
-    res, env = run_workload(cs, dev, comm, env_name, n, B, mode, K, W, kernel, rank=rank)
+    res, env, _ = run_workload(cs, dev, comm, env_name, n, B, mode, K, W, kernel, rank=rank)
     del env
     torch.cuda.empty_cache()
     return {"key": key, "workload": label, "mode": mode, "kernel": kernel, "steps": K, "warmup": W, **res}
@@ -826,21 +890,23 @@ def dry_run(a, rank, world):
         dist.all_gather(gathered, part)
         part = torch.stack(gathered).sum(0)
         # the fields of the real line that only exist at N > 1, through the same code (gloo instead of RCCL; fabricated rates)
-        allgather_us = time_metric_allgather(dist, torch.device("cpu"), reps=20, torch=torch)
+        if a.full:
+            allgather_us = time_metric_allgather(dist, torch.device("cpu"), reps=20, torch=torch)
         comm = Comm(world, torch.device("cpu"), True, True)
         rates = comm.gather(1.0e9 + rank)
         per_rank = {"min": min(rates), "median": statistics.median(rates), "max": max(rates), "slowest_rank": rates.index(min(rates)),
                     "unit": "env-steps/s per GPU (fabricated: 1e9 + rank)"}
     if rank == 0:
-        print(json.dumps(_fits({"metric": "env-steps/sec", "value": None, "unit": "env-steps/s", "n_gpus": world,
-                          "steps": a.steps, "warmup": a.warmup, "dry_run": True,
-                          "eval": {"envs": int(part[3].item()), "world_size": world, "allgather_us": allgather_us},
-                          "per_rank_value": per_rank,
-                          "also_at_this_n": "all" if (world == 1 or a.also) else "c5 weak + c5 strong only",
-                          "c5_strong_total": {"value": None, "n_gpus": world, "envs_total": C5_GLOBAL_BATCH,
-                                              "envs_per_gpu": C5_GLOBAL_BATCH // world if C5_GLOBAL_BATCH % world == 0 else None},
-                          "c5_weak_total": {"value": None, "n_gpus": world, "envs_total": 8192 * world, "envs_per_gpu": 8192}})),
-              flush=True)
+        line = {"metric": "env-steps/sec", "value": None, "unit": "env-steps/s", "n_gpus": world,
+                "steps": a.steps, "warmup": a.warmup, "dry_run": True,
+                "eval": {"envs": int(part[3].item()), "world_size": world, "allgather_us": allgather_us},
+                "per_rank_value": per_rank}
+        if a.full:
+            line.update({"also_at_this_n": "all" if (world == 1 or a.also) else "c5 weak + c5 strong only",
+                         "c5_strong_total": {"value": None, "n_gpus": world, "envs_total": C5_GLOBAL_BATCH,
+                                             "envs_per_gpu": C5_GLOBAL_BATCH // world if C5_GLOBAL_BATCH % world == 0 else None},
+                         "c5_weak_total": {"value": None, "n_gpus": world, "envs_total": 8192 * world, "envs_per_gpu": 8192}})
+        print(json.dumps(_fits(line)), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -965,8 +1031,11 @@ def main():
     mode = a.mode or "rollout"
     K, W = a.steps, a.warmup
 
-    res, env = run_workload(cs, dev, comm, env_name, n, B, mode, K, W, a.kernel, rank=rank, no_graph=a.no_graph,
-                            min_gpu_s=a.min_gpu_s)
+    dump = bool(a.dump_outputs) and rank == 0
+    res, env, outputs = run_workload(cs, dev, comm, env_name, n, B, mode, K, W, a.kernel, rank=rank, no_graph=a.no_graph,
+                                     min_gpu_s=a.min_gpu_s if a.full else None, dump=dump)
+    if dump:
+        write_outputs(outputs, a.dump_outputs)
 
     # evaluation-metric reduction (runner.py:86-96): the path's only collective, outside the timed region
     part = env.metric_partials().clone().to(comm.cdev)
@@ -983,7 +1052,7 @@ def main():
             comm.pg = False
     part = part.cpu().numpy()
     allgather_us = None
-    if pg:
+    if pg and a.full:
         try:
             allgather_us = time_metric_allgather(dist, comm.cdev, torch=torch, sync=lambda: torch.cuda.synchronize(dev))
         except Exception as exc:   # noqa: BLE001
@@ -1002,7 +1071,7 @@ def main():
             "config": {"workload": f"{env_name}, {n} agents, {m} targets, batch={B} envs per GPU, agent_mode=0, "
                                    f"target_mode=0 ({a.workload})", "mode": mode,
                        "steps_per_launch": res["steps_per_launch"], "auto_reset": True, "emits": "obs+state every step",
-                       "kernel": a.kernel, "hip_graph": mode == "step" and not a.no_graph,
+                       "kernel": a.kernel, "hip_graph": mode == "step" and not a.no_graph, "full": a.full,
                        "backend": ("gloo (BENCH_SHARE_GPU test mode)" if share else "nccl (RCCL)") if pg else None,
                        "cpu_binding": cpu_binding,
                        **({"backend_error": pg_error} if pg_error else {})},
@@ -1018,7 +1087,7 @@ def main():
             "per_rank_value": res["per_rank_value"],
         }
     also = []
-    if not a.no_also and a.workload == "c2" and not a.batch:
+    if a.full and not a.no_also and a.workload == "c2" and not a.batch:
         # c5 (BASELINE config 5: flight_easy 5a15t, 65536 envs over the node) at every N: the weak point (8192 per GPU,
         # = the 8-GPU configuration's per-GPU share) and the strong point (65536 / N per GPU)
         also.append(side_measurement(cs, dev, comm, "c5w", "c5 weak: flight_easy 5a15t, 8192 envs per GPU", "flight_easy", 5,
@@ -1068,11 +1137,11 @@ def main():
                                  "envs_total": (C5_GLOBAL_BATCH if tag == "c5 strong" else 8192 * world),
                                  "envs_per_gpu": (C5_GLOBAL_BATCH // world if tag == "c5 strong" else 8192),
                                  "roofline_frac_per_gpu": ent["roofline"]["frac"]}
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(env_name, n, B)
-        # stdout carries the compact line (<= MAX_LINE characters); the full record goes to gpurun_out/bench_detail.json and,
-        # one entry per row, to stderr BEFORE the line (so the line stays the last thing this process prints)
-        detail = write_detail(line)
+        # stdout carries the compact line (<= MAX_LINE characters); with --full the whole record goes to the detail file
+        # (write_detail) and, one entry per row, to stderr BEFORE the line (so the line stays the last thing this process prints)
+        detail = write_detail(line) if a.full else None
         for ent in also:
             fr = (ent.get("roofline") or {}).get("frac")
             sys.stderr.write(f"bench.py: also {ent.get('key'):>16}  {ent['value']:.4g} env-steps/s  "

@@ -105,6 +105,8 @@ def test_bench_gpus_flag_spawns_that_many_ranks():
     assert len([ln for ln in p.stdout.splitlines() if ln.startswith("{")]) == 1   # rank 0's line only
     assert line["n_gpus"] == 2 and line["eval"]["envs"] == 2 * 4096 and line["eval"]["world_size"] == 2
     assert line["steps"] == 20 and line["warmup"] == 5
+    # a plain run measures the headline only: no all-gather timing, no secondary workloads (those are --full's)
+    assert line["eval"]["allgather_us"] is None and "c5_strong_total" not in line and "also_at_this_n" not in line
 
 
 def test_bench_line_is_compact_whatever_the_record_holds():
@@ -153,7 +155,7 @@ def test_bench_eight_rank_control_flow():
     """The driver's 8-GPU launch, as far as a GPU-less container can take it: eight rank processes over gloo, the all-gather
     sees all eight shards, and BASELINE config 5 shows up as fields of its own (65536 envs = 8 x 8192: the strong and the
     weak point coincide at N = 8)."""
-    p, line = _run_bench(["--gpus", "8", "--dry-run", "--steps", "20", "--warmup", "5"], timeout=600)
+    p, line = _run_bench(["--gpus", "8", "--dry-run", "--steps", "20", "--warmup", "5", "--full"], timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     assert len(p.stdout) < 6000 and json.loads(p.stdout[-8000:]) == line   # what a consumer of the last 8 KB reads
     assert line["n_gpus"] == 8 and line["eval"]["envs"] == 8 * 4096 and line["eval"]["world_size"] == 8
@@ -313,3 +315,32 @@ def test_bench_launcher_propagates_rank_failure():
 def test_bench_rejects_world_size_mismatch():
     p, line = _run_bench(["--gpus", "2", "--dry-run"], env_extra={"RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0"})
     assert p.returncode != 0 and line is None and "WORLD_SIZE=1" in p.stderr
+
+
+def test_bench_options_and_output_sample():
+    """A plain run has no process group at N = 1 unless asked for; --full tries one (--pg auto).  --dump-outputs: every env
+    while the arrays fit in DUMP_MAX_BYTES, else the same fixed, seeded sample of envs for every array, as float32 (the
+    env indices as float64)."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod5", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.parse_args([]).pg == "off" and not bench.parse_args([]).full and bench.parse_args([]).dump_outputs is None
+    assert bench.parse_args(["--full"]).pg == "auto" and bench.parse_args(["--full", "--pg", "off"]).pg == "off"
+    assert bench.parse_args(["--force-pg"]).pg == "on" and bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+    B = 64
+    small = {"reward": torch.arange(B, dtype=torch.float32), "terminated": torch.arange(B, dtype=torch.uint8) % 2 == 1,
+             "obs": torch.arange(B * 12, dtype=torch.float32).reshape(B, 3, 4)}
+    got = bench.output_sample(small, B)
+    assert got["env_index"].dtype == np.float64 and np.array_equal(got["env_index"], np.arange(B))
+    assert got["terminated"].dtype == np.float32 and np.array_equal(got["terminated"], np.arange(B) % 2)
+    assert np.array_equal(got["obs"], small["obs"].numpy())
+    # a batch too big for the ceiling: flight-width obs rows (3 x 2504 floats per env)
+    B = 8192
+    big = {"reward": torch.arange(B, dtype=torch.float32), "obs": torch.zeros(B, 3, 2504).add_(torch.arange(B).view(B, 1, 1))}
+    a, b = bench.output_sample(big, B), bench.output_sample(big, B)
+    assert sum(x.nbytes for x in a.values()) <= bench.DUMP_MAX_BYTES < 64e6
+    idx = a["env_index"]
+    assert 1000 < len(idx) < B and np.array_equal(idx, b["env_index"]) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(a["reward"], idx) and np.array_equal(a["obs"][:, 2, 7], idx)

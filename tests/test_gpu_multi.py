@@ -69,7 +69,7 @@ def _tail_line(p, keep=8000):
 
 
 def test_bench_two_ranks_share_one_gpu_through_the_launcher(tmp_path):
-    p, line = _bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--min-gpu-s", "0.05"],
+    p, line = _bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--min-gpu-s", "0.05"],
                      {"BENCH_SHARE_GPU": "1", "BENCH_DETAIL_DIR": str(tmp_path)})
     assert p.returncode == 0, p.stderr[-3000:]
     assert line["n_gpus"] == 2 and line["steps"] == 20 and line["warmup"] == 5
@@ -90,10 +90,10 @@ def test_bench_two_ranks_share_one_gpu_through_the_launcher(tmp_path):
 
 
 def test_bench_default_line_fits_a_tail_consumer(tmp_path):
-    """The driver's own command shape (every secondary workload on, no --no-also): stdout is ONE line of less than 6000
+    """The full run (--full: every secondary workload on, no --no-also): stdout is ONE line of less than 6000
     characters that parses from the last 8000 characters of stdout; the 17 secondary workloads are [value, fraction] pairs in
     it and full entries in the detail file it names (r05: a 21.8 KB line, cut by its consumer, parsed = null)."""
-    p, line = _bench(["--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--min-gpu-s", "0.05"],
+    p, line = _bench(["--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--min-gpu-s", "0.05"],
                      {"BENCH_DETAIL_DIR": str(tmp_path)})
     assert p.returncode == 0, p.stderr[-3000:]
     assert p.stdout.count("\n") == 1 and len(p.stdout) < 6000 and _tail_line(p) == line
@@ -107,15 +107,52 @@ def test_bench_default_line_fits_a_tail_consumer(tmp_path):
     detail = json.load(open(line["detail"]))
     assert [e["key"] for e in detail["also"]] == list(summ)
     c3 = next(e for e in detail["also"] if e["key"] == "c3")
-    assert c3["roofline"]["frac"] == pytest.approx(summ["c3"][1], rel=2e-3) and c3["roofline"]["kernel"] == "k_rollout_od<5>"
+    # the summary carries the fraction to 3 significant digits (compact_line: sig(frac, 3))
+    assert summ["c3"][1] == float(f"{c3['roofline']['frac']:.3g}") and c3["roofline"]["kernel"] == "k_rollout_od<5>"
 
 
-def test_bench_single_gpu_line_is_single_clocked():
-    """value, ms_per_step and roofline.achieved come from the same HIP-event interval (VERDICT r1 weak #4)."""
-    p, line = _bench(["--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-also", "--min-gpu-s", "0.05"], {})
+def test_bench_single_gpu_line_is_single_clocked(tmp_path):
+    """value, ms_per_step and roofline.achieved come from the same HIP-event interval; --full repeats
+    the K-step region and takes the median."""
+    p, line = _bench(["--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-also", "--min-gpu-s", "0.05"],
+                     {"BENCH_DETAIL_DIR": str(tmp_path)})
     assert p.returncode == 0, p.stderr[-3000:]
     assert line["n_gpus"] == 1 and line["timing"]["repeats"] >= 5
     per_step_s = line["ms_per_step"] / 1e3
     assert line["value"] == pytest.approx(4096 / per_step_s, rel=1e-9)
     assert line["roofline"]["achieved"] == pytest.approx(294 * line["value"] / 1e9, rel=1e-9)
     assert line["roofline"]["avg_launch_us"] == pytest.approx(per_step_s * 20 * 1e6, rel=1e-9)
+
+
+def test_bench_plain_run_times_the_steps_once_and_dumps_the_last_step(tmp_path):
+    """A plain run times exactly --steps steps (one K-step region) and measures nothing else; --dump-outputs writes the
+    arrays the timed path returned in its last step, the same from run to run and equal to what the same rollouts give
+    in this process (the bench's seeds and actions: warm-up of one 20-step launch, then the timed one)."""
+    import numpy as np
+    dumps = [tmp_path / "a", tmp_path / "b"]
+    for d in dumps:
+        p, line = _bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(d)],
+                         {"BENCH_DETAIL_DIR": str(tmp_path / "detail")})
+        assert p.returncode == 0, p.stderr[-3000:]
+        assert p.stdout.count("\n") == 1 and _tail_line(p) == line
+        assert line["steps"] == 20 and line["timing"]["repeats"] == 1 and line["config"]["full"] is False
+        assert line["timing"]["region_ms_min_median_max"][1] == pytest.approx(line["ms_per_step"] * 20, rel=1e-5)
+        assert line["value"] == pytest.approx(4096 / (line["ms_per_step"] / 1e3), rel=1e-9)
+        for key in ("also_summary", "cpu_baseline", "detail", "c5_strong_total"):
+            assert key not in line, key
+        assert line["config"]["backend"] is None and line["eval"]["allgather_us"] is None
+    assert not (tmp_path / "detail").exists()
+    got = [{f.stem: np.load(f) for f in d.glob("*.npy")} for d in dumps]
+    assert set(got[0]) == {"reward", "terminated", "win", "obs", "state", "env_index"}
+    for name, arr in got[0].items():
+        assert arr.dtype == (np.float64 if name == "env_index" else np.float32), name
+        assert np.array_equal(arr, got[1][name]), name
+    assert np.array_equal(got[0]["env_index"], np.arange(4096))
+    env = cs.BatchedFlightEnv(cs.make_env_args("flight_easy", n_agents=3), batch=4096, freeze_done=False, auto_reset=True)
+    acts = torch.randint(0, 3, (20, 4096, 3), dtype=torch.int32, device="cuda",
+                         generator=torch.Generator(device="cuda").manual_seed(1))
+    env.rollout(acts)
+    want = env.rollout(acts)
+    assert got[0]["obs"].shape == (4096, 3, 4) and got[0]["state"].shape == (4096, env.state_shape)
+    for name in ("reward", "terminated", "win", "obs", "state"):
+        assert np.array_equal(got[0][name], want[name][-1].float().cpu().numpy()), name

@@ -57,6 +57,11 @@ def _clang_asan_runtime(hipcc):
 
 
 def test_host_half_of_the_product_under_asan_ubsan(tmp_path):
+    import torch
+    if torch.cuda.is_available():
+        # the clang ASan runtime intercepts the HIP runtime's device allocations (hsa_amd_memory_pool_allocate) once a GPU is
+        # visible: sanitizer runs of the product belong on the GPU-less host
+        pytest.skip("needs a GPU-less host")
     from cooperative_search_amd import build
     hipcc = build.hipcc_path()
     if hipcc is None:

@@ -15,7 +15,7 @@ for n in (3, 5):
             if kernel == "ode" and B > (1 << 15):
                 continue
             steps = 40 if B >= (1 << 22) else (400 if B >= (1 << 18) else 1000)   # 2^22: the output tables of 100 steps would not fit
-            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-also",
+            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-also",
                                   "--workload", "c2" if n == 3 else "c3", "--mode", "rollout", "--kernel", kernel,
                                   "--batch", str(B), "--steps", str(steps), "--warmup", str(min(100, steps))],
                                  capture_output=True, text=True).stdout.strip().splitlines()

@@ -4,12 +4,12 @@
 # runs keep their own stdout line (*_traced.json); the untraced lines are what the driver's run looks like.
 R="${GRAFT_REPO_ROOT:?}"; O="$R/gpurun_out/final"; rm -rf "$O"; mkdir -p "$O"
 cd "$R"
-python bench.py > "$O/bench_default.json" 2> "$O/bench_default.err"; echo "bench default rc=$?"; cp gpurun_out/bench_detail.json "$O/bench_default_detail.json"
-python bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver_args.json" 2> "$O/bench_driver_args.err"; echo "bench driver rc=$?"; cp gpurun_out/bench_detail.json "$O/bench_driver_args_detail.json"
+BENCH_DETAIL_DIR="$O" python bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err"; echo "bench default rc=$?"; mv "$O/bench_detail.json" "$O/bench_default_detail.json"
+BENCH_DETAIL_DIR="$O" python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$O/bench_driver_args.json" 2> "$O/bench_driver_args.err"; echo "bench driver rc=$?"; mv "$O/bench_detail.json" "$O/bench_driver_args_detail.json"
 wc -c "$O/bench_default.json" "$O/bench_driver_args.json"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d "$O/trace_default" -o p -- python3 "$R/bench.py" --no-cpu-baseline > "$O/trace_default.log" 2>&1; echo "trace default rc=$?"; cp "$R/gpurun_out/bench_detail.json" "$O/bench_default_traced_detail.json"
-rocprofv3 --kernel-trace --stats -d "$O/trace_driver" -o p -- python3 "$R/bench.py" --steps 20 --warmup 5 --no-cpu-baseline > "$O/trace_driver.log" 2>&1; echo "trace driver rc=$?"; cp "$R/gpurun_out/bench_detail.json" "$O/bench_driver_args_traced_detail.json"
+BENCH_DETAIL_DIR="$O" rocprofv3 --kernel-trace --stats -d "$O/trace_default" -o p -- python3 "$R/bench.py" --full --no-cpu-baseline > "$O/trace_default.log" 2>&1; echo "trace default rc=$?"; mv "$O/bench_detail.json" "$O/bench_default_traced_detail.json"
+BENCH_DETAIL_DIR="$O" rocprofv3 --kernel-trace --stats -d "$O/trace_driver" -o p -- python3 "$R/bench.py" --steps 20 --warmup 5 --full --no-cpu-baseline > "$O/trace_driver.log" 2>&1; echo "trace driver rc=$?"; mv "$O/bench_detail.json" "$O/bench_driver_args_traced_detail.json"
 cd "$R"
 grep -h '^{"metric"' "$O/trace_default.log" | tail -1 > "$O/bench_default_traced.json"
 grep -h '^{"metric"' "$O/trace_driver.log" | tail -1 > "$O/bench_driver_args_traced.json"
