@@ -1398,27 +1398,16 @@ __device__ __forceinline__ void emit_flush_store(const DevParams &p, const StepI
     io.reward[slot0 + pl.rtw] = f.reward;  // duplicates write the same value
     io.terminated[slot0 + pl.rtw] = (uint8_t)f.term;
     io.win[slot0 + pl.rtw] = (uint8_t)f.win;
-#ifndef CS_EMIT_NT
-#define CS_EMIT_NT 1
-#endif
     if (io.obs) {  // one float4 per (env, agent)
         float4 *dst = reinterpret_cast<float4 *>(io.obs + slot0 * N * (size_t)p.obs_row_w + pl.obs_out);
-#if CS_EMIT_NT
         const v4f nv = {f.obs.x, f.obs.y, f.obs.z, f.obs.w};
         __builtin_nontemporal_store(nv, reinterpret_cast<v4f *>(dst));
-#else
-        *dst = f.obs;
-#endif
     }
     if (io.state) {  // the wavefront's rows are contiguous in get_state's [B][W] layout
         float *dst = io.state + slot0 * (size_t)(4 * N + 3 * p.n_targets);
 #pragma unroll
         for (int k = 0; k < EmitPlan<N>::K; k++) {
-#if CS_EMIT_NT
             __builtin_nontemporal_store(f.st[k], dst + pl.st_out[k]);
-#else
-            dst[pl.st_out[k]] = f.st[k];
-#endif
         }
     }
 }
@@ -1497,15 +1486,12 @@ __device__ __forceinline__ void step_block(const DevParams &p, const StepIO &io,
     const int lane = threadIdx.x & 63;
     const bool live = b < p.B;
     // issue every independent global load before the barrier that publishes the trig table
-#ifndef CS_STEP_TAPE
-#define CS_STEP_TAPE 1
-#endif
     // The draws of a single step come from the env's hit tape while it is valid (left by a rollout call or cs_mt_advance;
     // it is never written here: tape_finish rebases it by the words consumed since), which takes the MT19937 window --
     // a load that depends on the header's cursor -- off the launch's critical path; otherwise words are twisted on demand.
     // (the rollout call of flight passes TAPE = false: nothing refreshes the tapes between its launches, and the step
     // role there is hidden behind the map sweep either way)
-    constexpr bool STEP_TAPE = CS_STEP_TAPE && TAPE && N <= 5;
+    constexpr bool STEP_TAPE = TAPE && N <= 5;
     Env<N> e;
     int act[N];
     TapeRaw traw = {};
@@ -1894,32 +1880,34 @@ inline dim3 map_grid(const DevParams &p) {
     return dim3((unsigned)p.B, (unsigned)((p.cells / 4 + MAP_ILP * MAP_BLOCK - 1) / (MAP_ILP * MAP_BLOCK)));
 }
 
+// The launch split of the rollout kernels: `vec` over the first `full` envs (whole wavefronts whose output blocks are 16-byte
+// aligned, so every store is a full-width one), `tail` -- plain stores, runtime checks -- over the rest; `per_block` envs per workgroup.
+using RolloutKernel = void (*)(DevParams, StepIO);
+void launch_split(RolloutKernel vec, unsigned vec_threads, RolloutKernel tail, unsigned tail_threads, int per_block, int full,
+                  const DevParams &p, StepIO io, size_t smem, hipStream_t s) {
+    if (full > 0) {
+        io.env0 = 0;
+        io.env_n = full;
+        hipLaunchKernelGGL(vec, dim3((unsigned)((full + per_block - 1) / per_block)), dim3(vec_threads), smem, s, p, io);
+    }
+    if (p.B - full > 0) {
+        io.env0 = full;
+        io.env_n = p.B - full;
+        hipLaunchKernelGGL(tail, dim3((unsigned)((p.B - full + per_block - 1) / per_block)), dim3(tail_threads), smem, s, p, io);
+    }
+}
 // Lane-per-env launch(es) of one chunk: a VEC launch over the full wavefronts when every step's block of get_state
 // rows is 16-byte aligned, a plain launch for the remaining < 64 envs (or for everything otherwise).
 template <int N>
 void launch_lane(const cs_config *cfg, const DevParams &p, StepIO io, size_t smem, hipStream_t s) {
     const size_t W = 4 * (size_t)cfg->n_agents + 3 * (size_t)cfg->n_targets;
     const bool aligned = io.state && (reinterpret_cast<size_t>(io.state) & 15) == 0 && ((size_t)p.B * W) % 4 == 0;
-    const int full = aligned ? (p.B / 64) * 64 : 0;
-    if (full > 0) {
-        io.env0 = 0;
-        io.env_n = full;
-        hipLaunchKernelGGL((k_rollout_lane<N, true>), dim3((unsigned)((full + BLOCK - 1) / BLOCK)), dim3(BLOCK), smem, s, p, io);
-    }
-    if (p.B - full > 0) {
-        io.env0 = full;
-        io.env_n = p.B - full;
-        hipLaunchKernelGGL((k_rollout_lane<N, false>), dim3((unsigned)((p.B - full + BLOCK - 1) / BLOCK)), dim3(BLOCK), smem, s, p, io);
-    }
+    launch_split(k_rollout_lane<N, true>, BLOCK, k_rollout_lane<N, false>, BLOCK, BLOCK, aligned ? (p.B / 64) * 64 : 0, p, io, smem, s);
 }
 inline size_t lane_smem(const cs_config *c) {
     const size_t W = 4 * (size_t)c->n_agents + 3 * (size_t)c->n_targets;
     return ((TRIG_ROWS * TRIG_COLS * 8 + 15) / 16) * 16 + (BLOCK / 64) * 64 * W * sizeof(float) +
-           (BLOCK / 64) * MT_N * sizeof(unsigned)   // + one MT19937 row per wavefront (in-loop refresh)
-#ifdef CS_LANE_PADLDS   /* experiment: extra LDS per workgroup, i.e. fewer wavefronts per SIMD (occupancy sensitivity) */
-           + CS_LANE_PADLDS
-#endif
-        ;
+           (BLOCK / 64) * MT_N * sizeof(unsigned);   // + one MT19937 row per wavefront (in-loop refresh)
 }
 #ifndef CS_LV_W_FROM
 #define CS_LV_W_FROM 524288   /* envs from which teams of up to 3 take the three-wavefronts-per-SIMD build of k_rollout_lanev (round 5, A/B on one box, two passes, % of the HBM roofline: 2^18 envs 44.6 / 44.0 two / three wavefronts, 2^19 46.5 / 49.9, 2^20 46.8 / 51.3, 2^22 50.2 / 54.5) */
@@ -1933,31 +1921,17 @@ void launch_lanev(const cs_config *cfg, const DevParams &p, StepIO io, hipStream
     const bool aligned = io.state && io.obs && (reinterpret_cast<size_t>(io.state) & 15) == 0 &&
                          (reinterpret_cast<size_t>(io.obs) & 15) == 0 && ((size_t)p.B * W) % 4 == 0;
     const int full = aligned ? (p.B / 64) * 64 : 0;
-    if (full > 0) {
-        io.env0 = 0;
-        io.env_n = full;
-        if constexpr (N <= 3) {
-            if (full >= CS_LV_W_FROM)   // three wavefronts per SIMD (see k_rollout_lanev)
-                hipLaunchKernelGGL((k_rollout_lanev<N, true, 3>), dim3((unsigned)((full + LV_BLOCK - 1) / LV_BLOCK)), dim3(LV_BLOCK), smem, s, p, io);
-            else
-                hipLaunchKernelGGL((k_rollout_lanev<N, true>), dim3((unsigned)((full + LV_BLOCK - 1) / LV_BLOCK)), dim3(LV_BLOCK), smem, s, p, io);
-        } else {
-            hipLaunchKernelGGL((k_rollout_lanev<N, true>), dim3((unsigned)((full + LV_BLOCK - 1) / LV_BLOCK)), dim3(LV_BLOCK), smem, s, p, io);
-        }
-    }
-    if (p.B - full > 0) {
-        io.env0 = full;
-        io.env_n = p.B - full;
-        hipLaunchKernelGGL((k_rollout_lanev<N, false>), dim3((unsigned)((p.B - full + LV_BLOCK - 1) / LV_BLOCK)), dim3(LV_BLOCK), smem, s, p, io);
-    }
+    constexpr int WV = N <= 3 ? 3 : lv_waves(N);   // teams of up to 3: three wavefronts per SIMD from CS_LV_W_FROM envs (see k_rollout_lanev)
+    const RolloutKernel vec = full >= CS_LV_W_FROM ? k_rollout_lanev<N, true, WV> : k_rollout_lanev<N, true>;
+    launch_split(vec, LV_BLOCK, k_rollout_lanev<N, false>, LV_BLOCK, LV_BLOCK, full, p, io, smem, s);
 }
 // Which lane-per-env kernel: k_rollout_lanev for teams of up to 5 (its in-loop MT19937 refresh tops up one env per wavefront
 // and step, which covers the draw rate of those teams), k_rollout_lane (+ the k_mt_advance pre-pass) for larger ones.
 inline bool use_lanev(const cs_config *c, int flags) {
-    if (c->n_agents > CS_LANE_REFRESH_MAX_N) return false;
+    if (c->n_agents > LANE_REFRESH_MAX_N) return false;
     if (flags & CS_KERNEL_LANEV) return true;
     if (flags & CS_KERNEL_LANE) return false;
-    return CS_LANEV_DEFAULT != 0;
+    return true;
 }
 // Octet launch(es): a VEC launch over the full wavefronts (8 envs each) when every step's block of get_state rows is
 // 16-byte aligned, a plain launch for the remaining < 8 envs (or for everything otherwise).
@@ -1965,21 +1939,10 @@ template <int N>
 void launch_oct(const cs_config *cfg, const DevParams &p, StepIO io, hipStream_t s) {
     const size_t W = 4 * (size_t)cfg->n_agents + 3 * (size_t)cfg->n_targets;
     const bool aligned = !io.state || ((reinterpret_cast<size_t>(io.state) & 15) == 0 && ((size_t)p.B * W) % 4 == 0);
-    const int full = aligned ? (p.B / OCT_ENVS) * OCT_ENVS : 0;
     constexpr int EPB = (OCT_BLOCK / 64) * OCT_ENVS;   // envs per workgroup
     io.min_ahead = 2 * cfg->n_agents * CS_MAX_TARGETS;  // rows are topped up in place whenever one runs low
-    if (full > 0) {
-        io.env0 = 0;
-        io.env_n = full;
-        const dim3 grid((unsigned)((full + EPB - 1) / EPB));
-        if (io.obs && io.state) hipLaunchKernelGGL((k_rollout_oct<N, true, true>), grid, dim3(OCT_BLOCK), 0, s, p, io);
-        else hipLaunchKernelGGL((k_rollout_oct<N, true, false>), grid, dim3(OCT_BLOCK), 0, s, p, io);
-    }
-    if (p.B - full > 0) {   // the tail (or an unaligned output tensor): plain stores, runtime checks
-        io.env0 = full;
-        io.env_n = p.B - full;
-        hipLaunchKernelGGL((k_rollout_oct<N, false, false>), dim3((unsigned)((p.B - full + EPB - 1) / EPB)), dim3(OCT_BLOCK), 0, s, p, io);
-    }
+    const RolloutKernel vec = io.obs && io.state ? k_rollout_oct<N, true, true> : k_rollout_oct<N, true, false>;
+    launch_split(vec, OCT_BLOCK, k_rollout_oct<N, false, false>, OCT_BLOCK, EPB, aligned ? (p.B / OCT_ENVS) * OCT_ENVS : 0, p, io, 0, s);
 }
 // Octet-pair launch(es): like launch_oct, one workgroup (K + D wavefront) per 8 envs.
 template <int N>
@@ -1989,20 +1952,13 @@ void launch_od(const cs_config *cfg, const DevParams &p, StepIO io, hipStream_t 
     // three wavefronts per 8 envs (K, D and the emitting E) while five such workgroups per CU hold the batch in one round
     const bool e3 = (io.flags & CS_KERNEL_ODE) || (!(io.flags & CS_KERNEL_OD) && p.B <= CS_ODE_UPTO);
     io.min_ahead = 2 * cfg->n_agents * CS_MAX_TARGETS;  // rows are topped up in place whenever one runs low
-    const int full = aligned ? (p.B / OCT_ENVS) * OCT_ENVS : 0;
-    if (full > 0) {
-        io.env0 = 0;
-        io.env_n = full;
-        const dim3 grid((unsigned)(full / OCT_ENVS));
-        if (io.obs && io.state && e3) hipLaunchKernelGGL((k_rollout_od<N, true, true, true>), grid, dim3(OD_BLOCK + 64), 0, s, p, io);
-        else if (io.obs && io.state) hipLaunchKernelGGL((k_rollout_od<N, true, true, false>), grid, dim3(OD_BLOCK), 0, s, p, io);
-        else hipLaunchKernelGGL((k_rollout_od<N, true, false, false>), grid, dim3(OD_BLOCK), 0, s, p, io);
-    }
-    if (p.B - full > 0) {   // the tail (or an unaligned output tensor): plain stores, runtime checks
-        io.env0 = full;
-        io.env_n = p.B - full;
-        hipLaunchKernelGGL((k_rollout_od<N, false, false, false>), dim3((unsigned)((p.B - full + OCT_ENVS - 1) / OCT_ENVS)), dim3(OD_BLOCK), 0, s, p, io);
-    }
+    const bool emit = io.obs && io.state;
+    RolloutKernel vec;
+    if (emit && e3) vec = k_rollout_od<N, true, true, true>;
+    else if (emit) vec = k_rollout_od<N, true, true, false>;
+    else vec = k_rollout_od<N, true, false, false>;
+    launch_split(vec, emit && e3 ? OD_BLOCK + 64 : OD_BLOCK, k_rollout_od<N, false, false, false>, OD_BLOCK, OCT_ENVS,
+                 aligned ? (p.B / OCT_ENVS) * OCT_ENVS : 0, p, io, 0, s);
 }
 // cs_rollout: the first-generation lane kernel's lower bound, by bench.py's protocol (round 3): 3 agents 65536 envs octet 7.8e9 against
 // lane 7.3e9, 98304 8.0 / 8.2, 131072 8.2 / 10.4; 5 agents (the 250-VGPR lane variant) 262144 octet 5.6e9 against lane 4.9e9,
@@ -2014,8 +1970,7 @@ void launch_od(const cs_config *cfg, const DevParams &p, StepIO io, hipStream_t 
 #define CS_LANEV_FROM 65536
 #endif
 inline long long lane_from(const cs_config *c) {
-    if (CS_LANEV_DEFAULT && c->n_agents <= CS_LANE_REFRESH_MAX_N) return CS_LANEV_FROM;
-    return c->n_agents <= 4 ? CS_LANE_FROM : CS_LANE_FROM_LARGE_TEAMS;
+    return c->n_agents <= LANE_REFRESH_MAX_N ? CS_LANEV_FROM : CS_LANE_FROM_LARGE_TEAMS;
 }
 // Kernel choice for flight_easy: one env per 16-lane group (lowest latency, fills the chip from B = 4096) or one
 // env per lane (no replicated arithmetic; wins once the batch gives every SIMD a wavefront anyway).
@@ -2193,18 +2148,21 @@ int cs_rollout(const cs_config *cfg, void *state_dev, const void *actions_dev, i
         rc = check_actions(actions_dev, (size_t)T * p.B * cfg->n_agents, flags, cfg->n_agents, (size_t)p.B, (hipStream_t)stream);
         if (rc) return rc;
     }
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)cfg->n_agents, W = 4 * n + 3 * (size_t)cfg->n_targets, B = (size_t)p.B;
+    const size_t obs_w = cfg->variant == 1 ? n * ((size_t)p.cells + 4) : n * 4, act_w = n * ((flags & CS_ACTIONS_I64) ? 8 : 4);
+    // the outputs of steps [t0, t0 + steps) as the StepIO of one launch
+    auto slice = [&](int t0, int steps) {
+        return StepIO{(const char *)actions_dev + (size_t)t0 * B * act_w, reward_dev + (size_t)t0 * B, terminated_dev + (size_t)t0 * B,
+                      win_dev + (size_t)t0 * B, obs_dev ? obs_dev + (size_t)t0 * B * obs_w : nullptr,
+                      state_out_dev ? state_out_dev + (size_t)t0 * B * W : nullptr, flags, steps};
+    };
     if (cfg->variant == 1) {
         // flight: k_step for step 0, then T - 1 launches of k_flight_pipe (the map sweep of step t beside the kinematics /
         // detection of step t + 1), then k_map for the last step's sweep -- enqueued back to back by this one call, each
         // writing its own [t] slice of the outputs
-        hipStream_t s = (hipStream_t)stream;
-        const size_t n = (size_t)cfg->n_agents, W = 4 * n + 3 * (size_t)cfg->n_targets, B = (size_t)p.B;
-        const size_t obs_w = n * ((size_t)p.cells + 4), act_w = n * ((flags & CS_ACTIONS_I64) ? 8 : 4);
         auto step_io = [&](int t) {
-            StepIO it{(const char *)actions_dev + (size_t)t * B * act_w, reward_dev + (size_t)t * B,
-                      terminated_dev + (size_t)t * B, win_dev + (size_t)t * B,
-                      obs_dev ? obs_dev + (size_t)t * B * obs_w : nullptr,
-                      state_out_dev ? state_out_dev + (size_t)t * B * W : nullptr, flags, 1};
+            StepIO it = slice(t, 1);
             it.job_parity = t & 1;
             return it;
         };
@@ -2225,44 +2183,31 @@ int cs_rollout(const cs_config *cfg, void *state_dev, const void *actions_dev, i
                                                         obs_dev ? obs_dev + (size_t)(T - 1) * B * obs_w : nullptr, 1, (T - 1) & 1));
         return launched("cs_rollout");
     }
-    StepIO io{actions_dev, reward_dev, terminated_dev, win_dev, obs_dev, state_out_dev, flags, T};
+    const StepIO io = slice(0, T);
     if (use_od_kernel(cfg, flags)) {
-        CS_DISPATCH_N(cfg->n_agents, launch_od<N>(cfg, p, io, (hipStream_t)stream));
+        CS_DISPATCH_N(cfg->n_agents, launch_od<N>(cfg, p, io, s));
     } else if (use_oct_kernel(cfg, flags)) {
-        CS_DISPATCH_N(cfg->n_agents, launch_oct<N>(cfg, p, io, (hipStream_t)stream));
+        CS_DISPATCH_N(cfg->n_agents, launch_oct<N>(cfg, p, io, s));
     } else if (use_lane_kernel(cfg, flags, true) && use_lanev(cfg, flags)) {
-        CS_DISPATCH_N(cfg->n_agents, launch_lanev<N>(cfg, p, io, (hipStream_t)stream));   // one launch: rows are refreshed inside the kernel
+        CS_DISPATCH_N(cfg->n_agents, launch_lanev<N>(cfg, p, io, s));   // one launch: rows are refreshed inside the kernel
     } else if (use_lane_kernel(cfg, flags, true)) {
         // LANE_CHUNK steps per launch; before each chunk every env's MT19937 row is twisted fully ahead of its cursor by
         // a coalesced pre-pass, so the rollout loop itself (almost) never has to stop for a refill
-        hipStream_t s = (hipStream_t)stream;
-        const size_t n = (size_t)cfg->n_agents, W = 4 * n + 3 * (size_t)cfg->n_targets, B = (size_t)p.B;
-        const size_t act_w = n * ((flags & CS_ACTIONS_I64) ? 8 : 4);
         // (teams of up to 3 refresh their rows inside the kernel, one env per wavefront and step: one launch, no pre-pass)
-        const int chunk = cfg->n_agents <= CS_LANE_REFRESH_MAX_N ? T : LANE_CHUNK;
+        const int chunk = cfg->n_agents <= LANE_REFRESH_MAX_N ? T : LANE_CHUNK;
         for (int t0 = 0; t0 < T; t0 += chunk) {
             const int tc = T - t0 < chunk ? T - t0 : chunk;
-            if (tc >= 8 && cfg->n_agents > CS_LANE_REFRESH_MAX_N)
+            if (tc >= 8 && cfg->n_agents > LANE_REFRESH_MAX_N)
                 hipLaunchKernelGGL(k_mt_advance, dim3((unsigned)((p.B + 3) / 4)), dim3(256), 0, s, p, prepass_min_ahead(cfg, tc));
-            StepIO it{(const char *)actions_dev + (size_t)t0 * B * act_w, reward_dev + (size_t)t0 * B,
-                      terminated_dev + (size_t)t0 * B, win_dev + (size_t)t0 * B,
-                      obs_dev ? obs_dev + (size_t)t0 * B * n * 4 : nullptr,
-                      state_out_dev ? state_out_dev + (size_t)t0 * B * W : nullptr, flags, tc};
-            CS_DISPATCH_N(cfg->n_agents, launch_lane<N>(cfg, p, it, lane_smem(cfg), s));
+            CS_DISPATCH_N(cfg->n_agents, launch_lane<N>(cfg, p, slice(t0, tc), lane_smem(cfg), s));
         }
     } else if (flags & (CS_KERNEL_SOLO | CS_KERNEL_DUO)) {
         return fail(CS_E_CONFIG, "k_rollout / k_rollout_duo (the 16-lanes-per-env rollout kernels of rounds 1-2) were removed in round 6: "
                                  "CS_KERNEL_GROUP runs a rollout as T launches of the 16-lane step kernel");
     } else {
         // CS_KERNEL_GROUP without the round-2 rollout kernels: T launches of the 16-lane step kernel, each on its own [t] slice
-        hipStream_t s = (hipStream_t)stream;
-        const size_t n = (size_t)cfg->n_agents, W = 4 * n + 3 * (size_t)cfg->n_targets, B = (size_t)p.B;
-        const size_t act_w = n * ((flags & CS_ACTIONS_I64) ? 8 : 4);
         for (int t = 0; t < T; t++) {
-            StepIO it{(const char *)actions_dev + (size_t)t * B * act_w, reward_dev + (size_t)t * B, terminated_dev + (size_t)t * B,
-                      win_dev + (size_t)t * B, obs_dev ? obs_dev + (size_t)t * B * n * 4 : nullptr,
-                      state_out_dev ? state_out_dev + (size_t)t * B * W : nullptr, flags, 1};
-            CS_DISPATCH_N(cfg->n_agents, hipLaunchKernelGGL((k_step<N, 0>), dim3(env_blocks(p)), dim3(BLOCK), 0, s, p, it));
+            CS_DISPATCH_N(cfg->n_agents, hipLaunchKernelGGL((k_step<N, 0>), dim3(env_blocks(p)), dim3(BLOCK), 0, s, p, slice(t, 1)));
         }
     }
     return launched("cs_rollout");
@@ -2287,11 +2232,7 @@ int cs_rollout_policy(const cs_config *cfg, void *state_dev, const float *packed
     io.min_ahead = prepass_min_ahead(cfg, T);   // rows with fewer twisted words are topped up in the kernel's prologue
     PolicyIO pio{packed_dev, hidden_dev, last_dev, actions_dev, eps->epsilon, eps->anneal, eps->min_epsilon, eps->per_step,
                  eps->eps_dev, eps->trace_dev, seed, step0, row0, select};
-#if CS_POLICY_F16
 #define CS_RP_LDS(NN) ((size_t)16 * (NN) * (2 * HXS * 2 + 6 * HST * 2 + LDW * 4))   /* x, b, hs[2] plane pairs of halves + s_h fp32, per row */
-#else
-#define CS_RP_LDS(NN) ((size_t)3 * 16 * (NN) * LDW * 4)
-#endif
     const size_t lds = CS_RP_LDS(cfg->n_agents);
 #define CS_LAUNCH_RP(NN)                                                                                               \
     case NN: {                                                                                                         \

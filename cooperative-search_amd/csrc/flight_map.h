@@ -76,17 +76,8 @@ __device__ __forceinline__ void build_rowbits(const DevParams &p, const double (
 // holds many of them and one workgroup's load latency overlaps another's arithmetic and stores.  The pending-
 // update flags are written only by k_step / k_reset (set or cleared on every launch), never here, so the
 // workgroups of one env need no ordering; `apply` = 0 makes this a pure get_obs sweep (cs_emit).
-#ifndef CS_MAP_BLOCK
-#define CS_MAP_BLOCK 256
-#endif
-#ifndef CS_MAP_NT
-#define CS_MAP_NT 1
-#endif
-#ifndef CS_MAP_ILP
-#define CS_MAP_ILP 1
-#endif
-constexpr int MAP_BLOCK = CS_MAP_BLOCK;
-constexpr int MAP_ILP = CS_MAP_ILP;   // float4 chunks per thread, all loaded before the first is processed
+constexpr int MAP_BLOCK = 256;
+constexpr int MAP_ILP = 1;   // float4 chunks per thread, all loaded before the first is processed
 
 // The pending pass(es) applied to float4 chunk c of an env's map: true if a cell changed (flight_env.py:275-303).
 __device__ __forceinline__ bool map_update_chunk(const DevParams &p, const MapPassLds *s_pass, bool dirty, bool reset_pass, int c,
@@ -209,11 +200,7 @@ __device__ __forceinline__ void map_sweep(const DevParams &p, MapPassLds *s_pass
             const v4f nv = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (int a = 0; a < N; a++) {  // write-once stream: keep it out of the caches
-#if CS_MAP_NT
                 __builtin_nontemporal_store(nv, reinterpret_cast<v4f *>(obs + ((size_t)b * N + a) * row_w) + c);
-#else
-                reinterpret_cast<v4f *>(obs + ((size_t)b * N + a) * row_w)[c] = nv;
-#endif
             }
         }
     }
@@ -227,10 +214,7 @@ __global__ __launch_bounds__(MAP_BLOCK) void k_map(DevParams p, float *obs, int 
 
 // The update alone (no observation rows wanted): without the n output copies to hide it, the sweep is bound by the
 // per-workgroup prologue (job record -> lattice bitmap -> barrier), so one workgroup per env does the whole map.
-#ifndef CS_MAP_UPD_BLOCK
-#define CS_MAP_UPD_BLOCK 256
-#endif
-constexpr int MAP_UPD_BLOCK = CS_MAP_UPD_BLOCK;
+constexpr int MAP_UPD_BLOCK = 256;
 constexpr int MAP_UPD_ILP = (CS_MAX_MAP * CS_MAX_MAP / 4 + MAP_UPD_BLOCK - 1) / MAP_UPD_BLOCK;
 template <int N>
 __global__ __launch_bounds__(MAP_UPD_BLOCK) void k_map_update(DevParams p, int parity) {
@@ -244,17 +228,12 @@ __global__ __launch_bounds__(MAP_UPD_BLOCK) void k_map_update(DevParams p, int p
 // shadow instead of costing a serial ~10 us of their own.  The step's registers cap the occupancy at four workgroups
 // per CU (at the price of a 12-byte spill in the step role), so each sweep thread keeps PIPE_ILP float4 loads in flight
 // (measured: the sweep alone loses nothing at that occupancy, profiles/r02_flight_pipe.md).
-#ifndef CS_PIPE_ILP
-#define CS_PIPE_ILP 3
-#endif
-#ifndef CS_PIPE_WAVES
-#define CS_PIPE_WAVES 4   // wavefronts per SIMD the register budget must allow (<= 128 VGPRs): four workgroups per CU
-#endif
+// Wavefronts per SIMD the register budget must allow: four for teams of up to 3 (<= 128 VGPRs: four workgroups per CU).
 // Larger teams get a larger register budget instead of spills: at four wavefronts per SIMD (128 VGPRs) the step role of teams of 4..8
 // spilled 105..473 VGPRs; with three (168) teams of 4 and 5 spill nothing, with two (256) neither do teams of 6..8.  Measured, flight
 // B = 8192, us per step of cs_rollout: 5 agents 107.0 -> 100.2, 8 agents 179.7 -> 169.8 (three) -> 160.3 (two).
-constexpr int pipe_waves(int n) { return n <= 3 ? CS_PIPE_WAVES : (n <= 5 ? 3 : 2); }
-constexpr int PIPE_ILP = CS_PIPE_ILP;
+constexpr int pipe_waves(int n) { return n <= 3 ? 4 : (n <= 5 ? 3 : 2); }
+constexpr int PIPE_ILP = 3;
 template <int N>
 __global__ __launch_bounds__(BLOCK, pipe_waves(N)) void k_flight_pipe(DevParams p, StepIO io, float *map_obs, int map_parity,
                                                                       int nstep, int stride, int ysplit) {

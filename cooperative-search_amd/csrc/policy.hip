@@ -6,20 +6,20 @@
 //     x  = [obs(4) | one_hot(last_action)(A) | one_hot(agent_id)(n)]        (agent.py:41-52)
 //     h1 = relu(W1 x + b1);  h' = GRUCell(h1, h);  q = W3 relu(W2 h' + b2) + b3
 //     action = argmax_a q  (greedy)  or uniform over actions with probability epsilon
-// The GEMM-shaped products run on the fp32 matrix cores (v_mfma_f32_16x16x4_f32: exact fp32 products and sums,
-// 32 cycles per 16x16x4 block).  flight adds k_conv_features (below) for the conv front end of its network.
+// The GEMM-shaped products run on the 16-bit matrix cores with split-fp16 operands (k_policy_h below).  flight adds
+// k_conv_features (below) for the conv front end of its network.
 //
 // Decomposition (measured alternatives are listed in DESIGN.md section 8): a BLOCK of 4 wavefronts owns a tile of 16
-// rows and wavefront w computes column tile w (16 of the 64 hidden columns) of every layer, 120 MFMAs per tile:
-//   * its 120 weight fragments (one float per lane each, pre-packed on the host in lane order) are loaded ONCE into
-//     registers; the grid is persistent (as many blocks as the device holds) and loops over row tiles;
-//   * activations move from the C/D layout (col = lane&15, row = 4*(lane>>4)+reg) to the A layout (row = lane&15,
-//     k = lane>>4) through block-shared LDS, one barrier per layer;
+// rows and wavefront w computes column tile w (16 of the 64 hidden columns) of every layer:
+//   * its weight fragments (pre-packed on the host in lane order) are loaded ONCE into registers; the grid is
+//     persistent (as many blocks as the device holds) and loops over row tiles;
+//   * activations move from the C/D layout of the matrix instructions to their A layout through block-shared LDS,
+//     one barrier per layer;
 //   * the next tile's inputs are fetched into registers while the current one computes, and nothing inside the loop
 //     issues a global LOAD other than that prefetch (loads and stores share one in-order counter on this hardware:
 //     waiting for any load also waits for every store in flight);
-//   * the six GRU accumulator chains are interleaved so that consecutive MFMAs are independent (a dependent pair
-//     costs 40 cycles instead of 32); the gate nonlinearities use the hardware exp2 / rcp units.
+//   * the GRU accumulator chains are interleaved so that consecutive matrix instructions are independent; the gate
+//     nonlinearities use the hardware exp2 / rcp units.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -49,179 +49,10 @@ struct PolicyParams {
     int64_t *actions;        // [rows]
 };
 
-#ifdef POL_TIMELINE
-// debug build only: per-phase s_memtime stamps of thread 0 / block 0 (read by tools/exp_policy_timeline.py of round 4: git history)
-__device__ unsigned long long g_pstamps[32][8];
-#define POL_STAMP(k) do { if (blockIdx.x == 0 && threadIdx.x == 0 && iter < 32) g_pstamps[iter][k] = __builtin_readcyclecounter(); } while (0)
-#else
-#define POL_STAMP(k) do {} while (0)
-#endif
-
-// acc += A(16 x 4*KSTEPS, LDS row-major with stride LDW) * B(register-resident fragments)
-template <int KSTEPS>
-__device__ __forceinline__ f32x4 mfma_chain(const float *a_lds, const float (&bfrag)[KSTEPS], int lane, f32x4 acc) {
-#pragma unroll
-    for (int kk = 0; kk < KSTEPS; kk++) {
-        const float a = a_lds[(lane & 15) * LDW + 4 * kk + (lane >> 4)];
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bfrag[kk], acc, 0, 0, 0);
-    }
-    return acc;
-}
-
-template <int KS1>   // k-steps of fc1: 4 (inputs <= 16 wide) or 8 (<= 32 wide: conv features in front)
-__global__ __launch_bounds__(PBLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_policy(PolicyParams p) {
-    __shared__ float s_a[16 * LDW];      // x, then h'
-    __shared__ float s_b[16 * LDW];      // h1, then f
-    __shared__ float s_h[16 * LDW];      // previous hidden state
-    __shared__ float s_q[4][16 * 17];    // partial q of the four wavefronts
-    __shared__ float s_b3[16];
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;  // w is wave-uniform
-    const int crow = (lane >> 4) * 4, ccol = lane & 15;
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-
-    // every weight fragment this wavefront will use (120 floats per lane) and its biases, once
-    float b1[KS1], bg[6][16], b2[16], b3f[4];
-    const unsigned ulane = lane;  // uniform base + 32-bit lane offset
-#pragma unroll
-    for (int kk = 0; kk < KS1; kk++) b1[kk] = (p.w + OFF_W1 + (w * (KIN_MAX / 4) + kk) * FR)[ulane];
-#pragma unroll
-    for (int g = 0; g < 3; g++)   // torch.nn.GRUCell: gates ordered r, z, n in weight_ih / weight_hh
-#pragma unroll
-        for (int kk = 0; kk < 16; kk++) {
-            bg[2 * g][kk] = (p.w + OFF_WIH + ((w + 4 * g) * 16 + kk) * FR)[ulane];
-            bg[2 * g + 1][kk] = (p.w + OFF_WHH + ((w + 4 * g) * 16 + kk) * FR)[ulane];
-        }
-#pragma unroll
-    for (int kk = 0; kk < 16; kk++) b2[kk] = (p.w + OFF_W2 + (w * 16 + kk) * FR)[ulane];
-#pragma unroll
-    for (int kk = 0; kk < 4; kk++) b3f[kk] = (p.w + OFF_W3 + (4 * w + kk) * FR)[ulane];
-    if (threadIdx.x < 16) s_b3[threadIdx.x] = p.w[OFF_B3 + threadIdx.x];  // visible after the first barrier
-    const int col = 16 * w + ccol;
-    const float bias1 = p.w[OFF_B1 + col], bias2 = p.w[OFF_B2 + col];
-    const float bir = p.w[OFF_BIH + col], biz = p.w[OFF_BIH + 64 + col], bin = p.w[OFF_BIH + 128 + col];
-    const float bhr = p.w[OFF_BHH + col], bhz = p.w[OFF_BHH + 64 + col], bhn = p.w[OFF_BHH + 128 + col];
-
-    // staging: 16 threads per row, NCOL input columns and four hidden values each.  Input row (agent.py:41-52,
-    // base_net.py:31-39): [16 conv features |] obs(4) | one_hot(last action) | one_hot(agent id); raw mode (no `last`):
-    // [16 conv features |] the caller's own columns.
-    constexpr int NCOL = KS1 / 4;
-    const int tiles = (p.rows + 15) / 16;
-    const int fbase = p.feat ? NFEAT : 0, in_dim = fbase + 4 + p.n_actions + p.n_agents;
-    const int srow = threadIdx.x >> 4, kcol = threadIdx.x & 15;
-    enum { ZERO, OBS, FEAT, LAST, AGENT };
-    int kind[NCOL], kidx[NCOL];
-#pragma unroll
-    for (int j = 0; j < NCOL; j++) {
-        const int k = kcol + 16 * j, ko = k - fbase;
-        kind[j] = k >= in_dim ? ZERO : k < fbase ? FEAT : (!p.last || ko < 4) ? OBS : ko < 4 + p.n_actions ? LAST : AGENT;
-        kidx[j] = kind[j] == FEAT ? k : kind[j] == OBS ? ko : kind[j] == LAST ? ko - 4 : ko - 4 - p.n_actions;
-    }
-    float xv[NCOL];   // float inputs (obs / feature columns)
-    int lav[NCOL];    // last action of the row (one-hot(last action) columns)
-    float4 hv;
-    auto fetch = [&](int tile) {   // loads only: nothing here waits for memory
-        const int row = 16 * tile + srow < p.rows ? 16 * tile + srow : p.rows - 1;
-#pragma unroll
-        for (int j = 0; j < NCOL; j++) {
-            xv[j] = kind[j] == OBS ? p.obs[(size_t)row * p.obs_stride + p.obs_offset + kidx[j]]
-                  : kind[j] == FEAT ? p.feat[(size_t)(row / p.rows_per_feat) * NFEAT + kidx[j]] : 0.0f;
-            lav[j] = kind[j] == LAST ? (int)p.last[row] : -1;
-        }
-        hv = *reinterpret_cast<const float4 *>(p.hidden + (size_t)row * H + 4 * kcol);
-    };
-    auto input_value = [&](int j, int row) {
-        if (kind[j] == OBS || kind[j] == FEAT) return xv[j];
-        if (kind[j] == LAST) return kidx[j] == lav[j] ? 1.0f : 0.0f;
-        return (kind[j] == AGENT && kidx[j] == row % p.n_agents) ? 1.0f : 0.0f;
-    };
-
-    int tile = blockIdx.x;
-    if (tile < tiles) fetch(tile);
-    for (int iter = 0; tile < tiles; tile += gridDim.x, iter++) {
-        const int row0 = 16 * tile;
-        POL_STAMP(0);
-#pragma unroll
-        for (int j = 0; j < NCOL; j++)
-            s_a[srow * LDW + kcol + 16 * j] = input_value(j, row0 + srow < p.rows ? row0 + srow : p.rows - 1);
-        *reinterpret_cast<float4 *>(s_h + srow * LDW + 4 * kcol) = hv;
-        if (tile + (int)gridDim.x < tiles) fetch(tile + gridDim.x);
-        __syncthreads();
-        POL_STAMP(1);
-
-        {   // h1 = relu(W1 x + b1), columns 16w..16w+15
-            const f32x4 acc = mfma_chain<KS1>(s_a, b1, lane, zero);
-#pragma unroll
-            for (int r = 0; r < 4; r++) s_b[(crow + r) * LDW + col] = fmaxf(acc[r] + bias1, 0.0f);
-        }
-        __syncthreads();
-        POL_STAMP(2);
-
-        {   // GRUCell, columns 16w..16w+15: six independent accumulator chains, interleaved
-            f32x4 ir = zero, iz = zero, in_ = zero, hr = zero, hz = zero, hn_ = zero;
-#pragma unroll
-            for (int kk = 0; kk < 16; kk++) {
-                const float ax = s_b[(lane & 15) * LDW + 4 * kk + (lane >> 4)];
-                const float ah = s_h[(lane & 15) * LDW + 4 * kk + (lane >> 4)];
-                ir = __builtin_amdgcn_mfma_f32_16x16x4f32(ax, bg[0][kk], ir, 0, 0, 0);
-                hr = __builtin_amdgcn_mfma_f32_16x16x4f32(ah, bg[1][kk], hr, 0, 0, 0);
-                iz = __builtin_amdgcn_mfma_f32_16x16x4f32(ax, bg[2][kk], iz, 0, 0, 0);
-                hz = __builtin_amdgcn_mfma_f32_16x16x4f32(ah, bg[3][kk], hz, 0, 0, 0);
-                in_ = __builtin_amdgcn_mfma_f32_16x16x4f32(ax, bg[4][kk], in_, 0, 0, 0);
-                hn_ = __builtin_amdgcn_mfma_f32_16x16x4f32(ah, bg[5][kk], hn_, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const float rg = sigmoidf_((ir[r] + bir) + (hr[r] + bhr));
-                const float zg = sigmoidf_((iz[r] + biz) + (hz[r] + bhz));
-                const float ng = tanhf_((in_[r] + bin) + rg * (hn_[r] + bhn));
-                const float hnew = (1.0f - zg) * ng + zg * s_h[(crow + r) * LDW + col];
-                s_a[(crow + r) * LDW + col] = hnew;  // s_a (x) was last read before the previous barrier
-                if (row0 + crow + r < p.rows) p.hidden[(size_t)(row0 + crow + r) * H + col] = hnew;
-            }
-        }
-        __syncthreads();
-        POL_STAMP(3);
-
-        {   // f = relu(W2 h' + b2), columns 16w..16w+15
-            const f32x4 acc = mfma_chain<16>(s_a, b2, lane, zero);
-#pragma unroll
-            for (int r = 0; r < 4; r++) s_b[(crow + r) * LDW + col] = fmaxf(acc[r] + bias2, 0.0f);
-        }
-        __syncthreads();
-        POL_STAMP(4);
-
-        {   // q = W3 f + b3: the 64-long reduction is split four ways over the wavefronts
-            const f32x4 acc = mfma_chain<4>(s_b + 16 * w, b3f, lane, zero);
-#pragma unroll
-            for (int r = 0; r < 4; r++) s_q[w][(crow + r) * 17 + ccol] = acc[r];
-        }
-        __syncthreads();
-        POL_STAMP(5);
-
-        // final sum, argmax and epsilon-greedy: one thread per row (wavefront 0 only; the others run ahead to the
-        // next tile's staging)
-        if (threadIdx.x < 16) {
-            const int row = row0 + threadIdx.x;
-            auto qf = [&](int a) {
-                const int o = threadIdx.x * 17 + a;
-                return ((s_q[0][o] + s_q[1][o]) + (s_q[2][o] + s_q[3][o])) + s_b3[a];
-            };
-            if (p.q && row < p.rows)
-                for (int a = 0; a < p.n_actions; a++) p.q[(size_t)row * p.n_actions + a] = qf(a);
-            const float eps = p.eps_env ? (float)p.eps_env[(row < p.rows ? row : p.rows - 1) / p.n_agents] : p.epsilon;
-            const int act = select_action(qf, p.n_actions, p.select, eps, p.seed, p.step, p.row0 + (unsigned long long)row);
-            if (row < p.rows) p.actions[row] = act;
-        }
-        POL_STAMP(6);
-    }
-}
-
-
-#if CS_POLICY_F16
-// k_policy on the 16-bit matrix pipe with split-fp16 operands (policy_dev.h): same decomposition -- a block of 4 wavefronts owns a
+// The policy forward on the 16-bit matrix pipe with split-fp16 operands (policy_dev.h): a block of 4 wavefronts owns a
 // 16-row tile, wavefront w the hidden columns 16w..16w+15 of every layer, weights resident in registers (32 B fragments: 128
-// VGPRs), activations through LDS as (hi, lo) plane pairs, one barrier per layer, the next tile's inputs prefetched -- with 48
-// matrix instructions of ~17 cycles per tile and wavefront instead of 120 of 32.  The fc1 input is padded to 32 columns (one k-step)
+// VGPRs), activations through LDS as (hi, lo) plane pairs, one barrier per layer, the next tile's inputs prefetched -- 48
+// matrix instructions of ~17 cycles per tile and wavefront (the fp32 form it replaced issued 120 of 32).  The fc1 input is padded to 32 columns (one k-step)
 // whether or not the conv features are present.
 __global__ __launch_bounds__(PBLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_policy_h(PolicyParams p) {
     __shared__ __attribute__((aligned(16))) _Float16 s_a[2][16 * HST];   // x, then h'      (hi, lo planes)
@@ -304,9 +135,8 @@ __global__ __launch_bounds__(PBLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         nlav[j] = -1;
     }
     nhv = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int iter = 0; tile < tiles; tile += gridDim.x, iter++) {
+    for (int iter = 0; tile < tiles; tile += gridDim.x, iter++) {   // (iter is unused: without it one branch of the compiled loop flips its sense)
         const int row0 = 16 * tile;
-        POL_STAMP(0);
 #pragma unroll
         for (int j = 0; j < NCOL; j++)
             split_store(s_a[0], s_a[1], srow * HST + kcol + 16 * j, input_value(j, row0 + srow < p.rows ? row0 + srow : p.rows - 1));
@@ -318,7 +148,6 @@ __global__ __launch_bounds__(PBLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         const bool more = tile + (int)gridDim.x < tiles;   // block-uniform
         if (more) fetch(tile + gridDim.x, nxv, nlav, nhv);
         __syncthreads();
-        POL_STAMP(1);
 
         {   // h1 = relu(W1 x + b1), columns 16w..16w+15 (the bias enters the accumulator)
             f32x4 hi = splat4(bias1), lo = zero;
@@ -329,7 +158,6 @@ __global__ __launch_bounds__(PBLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             for (int r = 0; r < 4; r++) split_store(s_b[0], s_b[1], (crow + r) * HST + col, fmaxf(split_sum(hi[r], lo[r]), 0.0f));
         }
         __syncthreads();
-        POL_STAMP(2);
 
         {   // GRUCell, columns 16w..16w+15 (gru_products / gru_cell of policy_dev.h: the very code the fused closed loop runs)
             h8 xh[2], xl[2], hh[2], hl[2];
@@ -348,7 +176,6 @@ __global__ __launch_bounds__(PBLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             }
         }
         __syncthreads();
-        POL_STAMP(3);
 
         {   // f = relu(W2 h' + b2), columns 16w..16w+15
             f32x4 hi = splat4(bias2), lo = zero;
@@ -362,7 +189,6 @@ __global__ __launch_bounds__(PBLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             for (int r = 0; r < 4; r++) split_store(s_b[0], s_b[1], (crow + r) * HST + col, fmaxf(split_sum(hi[r], lo[r]), 0.0f));
         }
         __syncthreads();
-        POL_STAMP(4);
 
         // q = W3 f + b3 and the choice, by ONE wavefront (no K split, no exchange of partial sums, no barrier: the other wavefronts go
         // on to the next tile's staging, which touches neither s_b nor s_q; wavefront 0 joins the next barrier when it is done)
@@ -383,7 +209,6 @@ __global__ __launch_bounds__(PBLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            POL_STAMP(5);
             // argmax and epsilon-greedy: one lane per row
             if (lane < 16) {
                 const int row = row0 + lane;
@@ -397,7 +222,6 @@ __global__ __launch_bounds__(PBLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();   // s_q[0] is free again (this wavefront's next tile)
         }
-        POL_STAMP(6);
         // first use of the next tile's inputs: here, not earlier (see above)
 #pragma unroll
         for (int j = 0; j < NCOL; j++) {
@@ -409,14 +233,13 @@ __global__ __launch_bounds__(PBLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         hv = nhv;
     }
 }
-#endif   // CS_POLICY_F16
 
 // ---- flight: conv front end of the agent network (network/base_net.py:9-18,31-36) ---------------------------------
 // Conv2d(1, 4, k=4, s=2) -> ReLU -> Conv2d(4, 1, k=3, s=1, p=1) -> ReLU -> Linear(576, 16) on the 50 x 50 probability
 // map (the reference's flight hyper-parameters, common/arguments.py:256-265; anything else stays on the torch path).
 // One block per map: the map and both conv outputs live in LDS (23 KB), the 16 x 576 linear weights in registers (36
 // per thread); persistent blocks loop over maps.  All agents of an env observe the same map (flight_env.py:223-230), so the
-// batched caller runs this once per ENV and k_policy fans the 16 features out to the env's rows.
+// batched caller runs this once per ENV and k_policy_h fans the 16 features out to the env's rows.
 constexpr int MAPW = 50, C1W = 24, C1P = 26, C1CH = 4, NPOS = C1W * C1W;
 
 struct ConvParams {
@@ -477,7 +300,7 @@ __global__ __launch_bounds__(PBLOCK, 4) void k_conv_features(ConvParams p) {
 
     // The next map is fetched into registers while this one computes, and a map's 16 features are stored one
     // iteration late: at the top of an iteration the only memory operations in flight are then the prefetch loads
-    // (loads and stores share one in-order counter, see k_policy).
+    // (loads and stores share one in-order counter, see k_policy_h).
     constexpr int NV = (MAPW * MAPW / 4 + PBLOCK - 1) / PBLOCK;   // float4 per thread and map
     static_assert(NV == 3, "three float4 per thread");
     float4 pre0, pre1, pre2;   // plain scalars: an indexed private array captured by a lambda ends up in LDS
@@ -609,7 +432,6 @@ int cs_policy_pack(const float *fc1_w, const float *fc1_b, const float *w_ih, co
         return CS_E_ARG;
     }
     for (int i = 0; i < PACKED_FLOATS; i++) packed[i] = 0.0f;
-#if CS_POLICY_F16
     // split_f16 carries a value as hi = fp16(v), lo = fp16((v - hi) * 2048): above fp16's range hi is inf and lo NaN.  A weight
     // there is refused here; activations are bounded by the weights and the inputs (|obs| <= 1, |h| < 1): the bound
     // an activation must keep is documented in include/coopsearch.h.
@@ -651,26 +473,6 @@ int cs_policy_pack(const float *fc1_w, const float *fc1_b, const float *w_ih, co
     for (int i = 0; i < 64; i++) packed[HOFF_B2 + i] = fc2a_b[i];
     for (int i = 0; i < n_actions; i++) packed[HOFF_B3 + i] = fc2b_b[i];
     return CS_OK;
-#endif
-    auto frag = [&](int off, int tiles, int ksteps, const float *w, int n_out, int k_in) {
-        for (int nt = 0; nt < tiles; nt++)
-            for (int kk = 0; kk < ksteps; kk++)
-                for (int l = 0; l < 64; l++) {
-                    const int n = 16 * nt + (l & 15), k = 4 * kk + (l >> 4);  // B[k][n] = W[n][k]
-                    packed[off + (nt * ksteps + kk) * FR + l] = (n < n_out && k < k_in) ? w[(size_t)n * k_in + k] : 0.0f;
-                }
-    };
-    frag(OFF_W1, 4, KIN_MAX / 4, fc1_w, 64, in_dim);
-    frag(OFF_WIH, 12, 16, w_ih, 192, 64);
-    frag(OFF_WHH, 12, 16, w_hh, 192, 64);
-    frag(OFF_W2, 4, 16, fc2a_w, 64, 64);
-    frag(OFF_W3, 1, 16, fc2b_w, n_actions, 64);
-    for (int i = 0; i < 64; i++) packed[OFF_B1 + i] = fc1_b[i];
-    for (int i = 0; i < 192; i++) packed[OFF_BIH + i] = b_ih[i];
-    for (int i = 0; i < 192; i++) packed[OFF_BHH + i] = b_hh[i];
-    for (int i = 0; i < 64; i++) packed[OFF_B2 + i] = fc2a_b[i];
-    for (int i = 0; i < n_actions; i++) packed[OFF_B3 + i] = fc2b_b[i];
-    return CS_OK;
 }
 
 // One forward of the shared agent network over `rows` = B*n rows (row r = env r / n_agents, agent r % n_agents).
@@ -690,24 +492,8 @@ int cs_policy_forward(const float *packed_dev, const float *obs_dev, int obs_str
     PolicyParams p{rows, n_agents, n_actions, obs_stride, obs_offset, epsilon, eps_env_dev, seed, step, row0, select, packed_dev, obs_dev, last_dev,
                    feat_dev, rows_per_feat, hidden_dev, q_dev, actions_dev};
     const int tiles = (rows + 15) / 16;
-#if CS_POLICY_F16
-    {
-        static const int resident = resident_blocks(k_policy_h);   // persistent grid: what the device holds at once
-        hipLaunchKernelGGL(k_policy_h, dim3(tiles < resident ? tiles : resident), dim3(PBLOCK), 0, (hipStream_t)stream, p);
-        if (hipGetLastError() != hipSuccess) {
-            snprintf(g_perr, sizeof(g_perr), "cs_policy_forward: kernel launch failed");
-            return CS_E_LAUNCH;
-        }
-        return CS_OK;
-    }
-#endif
-    if (in_dim <= 16) {
-        static const int resident = resident_blocks(k_policy<4>);   // persistent grid: what the device holds at once
-        hipLaunchKernelGGL(k_policy<4>, dim3(tiles < resident ? tiles : resident), dim3(PBLOCK), 0, (hipStream_t)stream, p);
-    } else {
-        static const int resident = resident_blocks(k_policy<8>);
-        hipLaunchKernelGGL(k_policy<8>, dim3(tiles < resident ? tiles : resident), dim3(PBLOCK), 0, (hipStream_t)stream, p);
-    }
+static const int resident = resident_blocks(k_policy_h);   // persistent grid: what the device holds at once
+    hipLaunchKernelGGL(k_policy_h, dim3(tiles < resident ? tiles : resident), dim3(PBLOCK), 0, (hipStream_t)stream, p);
     if (hipGetLastError() != hipSuccess) {
         snprintf(g_perr, sizeof(g_perr), "cs_policy_forward: kernel launch failed");
         return CS_E_LAUNCH;
@@ -739,10 +525,5 @@ int cs_policy_conv_features(const float *conv1_w_dev, const float *conv1_b_dev, 
 
 const char *cs_policy_last_error(void) { return g_perr; }
 
-#ifdef POL_TIMELINE
-int cs_policy_debug_read_stamps(unsigned long long *out) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pstamps), sizeof(unsigned long long) * 32 * 8) == hipSuccess ? 0 : -1;
-}
-#endif
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // cooperative-search_amd/csrc/policy_dev.h -- device-side definitions of the agent-network kernels shared by
-// policy.hip (k_policy, k_conv_features) and coopsearch.hip (k_rollout_policy, the fused policy + env rollout).
+// policy.hip (k_policy_h, k_conv_features) and coopsearch.hip (k_rollout_policy, the fused policy + env rollout).
 // Include inside the translation unit's anonymous namespace.
 #pragma once
 
@@ -11,23 +11,8 @@ constexpr int PBLOCK = 256;      // 4 wavefronts, one 16-column tile each
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-// packed weight fragments, in floats: fragment (column tile nt, k-step kk) holds, for lane l,
-// W[16*nt + (l & 15)][4*kk + (l >> 4)] -- the B operand of one 16x16x4 MFMA
-constexpr int FR = 64;
-constexpr int OFF_W1 = 0;                           // [4 col tiles][8 k-steps][64] (k-steps 4..7 zero when in_dim <= 16)
-constexpr int OFF_WIH = OFF_W1 + 4 * (KIN_MAX / 4) * FR;  // [12][16][64]
-constexpr int OFF_WHH = OFF_WIH + 12 * 16 * FR;     // [12][16][64]
-constexpr int OFF_W2 = OFF_WHH + 12 * 16 * FR;      // [4][16][64]
-constexpr int OFF_W3 = OFF_W2 + 4 * 16 * FR;        // [1][16][64]
-constexpr int OFF_B1 = OFF_W3 + 16 * FR;            // 64
-constexpr int OFF_BIH = OFF_B1 + 64;                // 192
-constexpr int OFF_BHH = OFF_BIH + 192;              // 192
-constexpr int OFF_B2 = OFF_BHH + 192;               // 64
-constexpr int OFF_B3 = OFF_B2 + 64;                 // 16
-constexpr int PACKED_FLOATS_F32 = OFF_B3 + 16;
-
 // ---------------------------------------------------------------------------------------------------------------------------
-// Split-fp16 matrix path (default).  The fp32 matrix pipe (v_mfma_f32_16x16x4_f32) runs at the vector rate, 1/16 of the 16-bit
+// Split-fp16 matrix path.  The fp32 matrix pipe (v_mfma_f32_16x16x4_f32) runs at the vector rate, 1/16 of the 16-bit
 // rate, and at 92 kFLOP per env-step it caps the closed loop at ~1.7e9 env-steps/s however fast the env is.  Here every fp32
 // operand v is carried as TWO fp16 numbers, v = hi + lo / 2048 with hi = fp16(v) and lo = fp16((v - hi) * 2048) -- 22 significant
 // bits, the low part pre-scaled so that it stays in fp16's normal range wherever hi is normal -- and a product a*b is evaluated as
@@ -37,14 +22,10 @@ constexpr int PACKED_FLOATS_F32 = OFF_B3 + 16;
 // an error of ~2.4e-7 per product, two orders below the 2e-5 parity bar with the reference network (network/base_net.py:31-46).
 // Values below fp16's normal range (6.1e-5) become subnormal halves; the matrix pipe multiplies those exactly (see split_f16).
 // ---------------------------------------------------------------------------------------------------------------------------
-#ifndef CS_POLICY_F16
-#define CS_POLICY_F16 1
-#endif
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 constexpr int HST = 72;                 // halves per LDS row of a split activation plane: rows 144 B apart, conflict-free 16-byte reads
 constexpr int HXS = 40;                 // ... of the 32-column input planes of the fused closed loop: rows 80 B apart, conflict-free too
 constexpr float LO_SCALE = 2048.0f, LO_INV = 1.0f / 2048.0f;
-constexpr float F16_MIN_NORMAL = 6.2e-5f;
 // packed weights, in dwords: fragment f = 2 planes (hi, lo) x 64 lanes x 4 dwords (8 halves): lane l of fragment (column tile nt,
 // k-step ks of 32) holds W[16 nt + (l & 15)][32 ks + 8 (l >> 4) + j], j = 0..7 -- the B operand of one 16x16x32 MFMA
 constexpr int FRAG_DW = 2 * 64 * 4;
@@ -58,18 +39,13 @@ constexpr int HOFF_BIH = HOFF_B1 + 64;
 constexpr int HOFF_BHH = HOFF_BIH + 192;
 constexpr int HOFF_B2 = HOFF_BHH + 192;
 constexpr int HOFF_B3 = HOFF_B2 + 64;
-constexpr int PACKED_FLOATS_F16 = HOFF_B3 + 16;
-constexpr int PACKED_FLOATS = CS_POLICY_F16 ? PACKED_FLOATS_F16 : PACKED_FLOATS_F32;
+constexpr int PACKED_FLOATS = HOFF_B3 + 16;
 
 // v -> (hi, lo) of the split representation (same code on the host for the weights, cs_policy_pack)
 // hi = fp16(v) whatever v's size: the gfx950 matrix pipe takes SUBNORMAL fp16 inputs exactly (tools/mfma_f16_denorm.hip, run by
 // tests/test_gpu_mfma_denorm.py: products of subnormal halves against the fp64 sum, 1.4e-7 = the fp32 accumulation).  The first
 // version zeroed hi below fp16's normal range "so that no subnormal is handed to the matrix pipe": a compare and a select per stored
-// element in phases that are bound by VALU issue (closed loop 5.90 -> 6.11e8 without them).  -DCS_SPLIT_GUARD=1 brings the guard back
-// for a pipe that flushes.
-#ifndef CS_SPLIT_GUARD
-#define CS_SPLIT_GUARD 0
-#endif
+// element in phases that are bound by VALU issue (closed loop 5.90 -> 6.11e8 without them).
 // float -> half, round to nearest even, subnormal results kept: the instruction is PINNED on the device.  Written as a C cast, the
 // conversions of split_f16 came out of the compiler differently in k_policy_h and in the fused loop once the subnormal guard was
 // gone, and the two kernels' hidden states -- which must agree bit for bit -- differed by an ulp in rare elements after ~50 steps
@@ -98,12 +74,7 @@ __host__ __device__ __forceinline__ float clamp_f16_range(float v) {
 }
 __host__ __device__ __forceinline__ void split_f16(float v, _Float16 &hi, _Float16 &lo) {
     v = clamp_f16_range(v);
-#if CS_SPLIT_GUARD
-    const float a = v < 0.0f ? -v : v;
-    hi = a < F16_MIN_NORMAL ? (_Float16)0.0f : (_Float16)v;
-#else
     hi = cvt_half(v);
-#endif
     lo = cvt_half((v - (float)hi) * LO_SCALE);
 }
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
@@ -151,7 +122,7 @@ __device__ __forceinline__ float split_sum(float hi, float lo) { return __builti
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ __forceinline__ float tanhf_(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
 
-#if CS_POLICY_F16 && (defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__))
+#if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
 // GRUCell (torch.nn.GRUCell: gates r, z, n in weight_ih / weight_hh) of one 16-row tile for a wavefront's 16 hidden columns, shared by
 // k_policy_h and the fused closed loop so that both walk the SAME products in the SAME order (their actions must agree bit for bit).
 //   r = sigmoid(W_ir x + b_ir + W_hr h + b_hr), z likewise: ONE accumulator chain each over [x | h] (K = 128: x's two k-steps, then

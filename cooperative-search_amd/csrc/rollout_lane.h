@@ -24,18 +24,9 @@
 // Results are bit-identical to the group kernels (same per-env arithmetic, same MT19937 word order);
 // tests/test_gpu_parity.py runs both.
 // =========================================================================================================
-#ifndef CS_LANE_REFRESH_MAX_N
-#define CS_LANE_REFRESH_MAX_N 5   /* measured at B = 262144: 4 agents 29.9 -> 34-38 %, 5 agents 23.5 -> 28 % */
-#endif
+constexpr int LANE_REFRESH_MAX_N = 5;   // in-loop refresh up to this team size; measured at B = 262144: 4 agents 29.9 -> 34-38 %, 5 agents 23.5 -> 28 %
 #ifndef CS_LANE_FROM_LARGE_TEAMS
-#define CS_LANE_FROM_LARGE_TEAMS 1048576   /* ... for teams of 5 and more agents (lane_from) */
-#endif
-#ifndef CS_LANE_FROM
-#define CS_LANE_FROM 131072     /* default kernel of cs_rollout from this many envs: one env per lane (65536: octet 7.6e9
-                                   against lane 7.1e9 env-steps/s at 3 agents, 5.0e9 against 4.8e9 at 5; 262144: 8.0 / 10.4) */
-#endif
-#ifndef CS_LANEV_DEFAULT
-#define CS_LANEV_DEFAULT 1      /* the lane-per-env kernel of teams of up to 5 is k_rollout_lanev (rollout_lanev.h) */
+#define CS_LANE_FROM_LARGE_TEAMS 1048576   /* cs_rollout from this many envs for teams above LANE_REFRESH_MAX_N: k_rollout_lane (lane_from) */
 #endif
 #ifndef CS_ODE_UPTO
 #define CS_ODE_UPTO 8192        /* ... up to this many envs with the third (emitting) wavefront: four 3-wavefront workgroups per CU (32 KB of LDS each since E refreshes the rows: 10240 envs would need a fifth and run 3.7e9 against the pair variant's 5.0e9) x 256 CUs x 8 envs */
@@ -44,14 +35,11 @@
 #define CS_OD_UPTO 16384        /* cs_rollout up to this many envs: the octet pair kernel */
 #endif
 #ifndef CS_OCT_FROM
-#define CS_OCT_FROM 16384       /* cs_rollout above this many envs (and below CS_LANE_FROM): one env per 8 lanes, one wavefront */
+#define CS_OCT_FROM 16384       /* cs_rollout above this many envs (and below lane_from): one env per 8 lanes, one wavefront */
 #endif
 constexpr int LANE_REFILL = 192;   // words twisted per refill (<= 227: independent of each other)
 constexpr int LANE_REFILL_MAX = 192;
-#ifndef CS_LANE_CHUNK
-#define CS_LANE_CHUNK 64
-#endif
-constexpr int LANE_CHUNK = CS_LANE_CHUNK;     // steps per launch of the lane kernel: cs_rollout twists every row ahead in between
+constexpr int LANE_CHUNK = 64;     // steps per launch of the lane kernel: cs_rollout twists every row ahead in between
 
 template <int N>
 struct EnvL {
@@ -309,7 +297,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_rollout_lane(DevParams p, StepIO i
     const int t16 = lane & (G - 1), gshift = lane & ~(G - 1), grp = lane >> 4;
     const unsigned tmask = p.n_targets >= 16 ? 0xffffu : ((1u << p.n_targets) - 1u);
     constexpr int LOW = 2 * N * CS_MAX_TARGETS;   // words one step can consume: every lane enters a step with that many twisted
-    constexpr bool REFRESH = N <= CS_LANE_REFRESH_MAX_N;   // in-loop refresh (above); larger teams rely on cs_rollout's pre-pass
+    constexpr bool REFRESH = N <= LANE_REFRESH_MAX_N;   // in-loop refresh (above); larger teams rely on cs_rollout's pre-pass
     unsigned *rowbuf = reinterpret_cast<unsigned *>(tiles + (size_t)(BLOCK / 64) * 64 * W) + wave * MT_N;
     RowRegs rr;
     int cand = -1;                                // env (lane) whose row is in flight in `rr`

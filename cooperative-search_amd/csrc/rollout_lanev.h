@@ -35,29 +35,15 @@
 // Wavefronts per SIMD the register budget must allow.  Measured (profiles/r04_lanev.md): the kernel wants ~210 VGPRs at 3 agents
 // and ~240 at 5; capped at 168 (three wavefronts) the 3-agent variant spills 23 registers and runs 40.6 % of the HBM roofline at
 // 2^18 envs against 44.0 % uncapped (4096 wavefronts = 1.33 resident rounds instead of 2 full ones) but 49.3 % against 46.0 % at
-// 2^20; the 5-agent variant spills 670 and halves.  So: two.
-#ifndef CS_LV_WAVES_SMALL
-#define CS_LV_WAVES_SMALL 2   /* teams of up to 3 */
-#endif
-#ifndef CS_LV_WAVES_MID
-#define CS_LV_WAVES_MID 2     /* teams of 4 and 5 */
-#endif
-#ifndef CS_LV_WAVES_LARGE
-#define CS_LV_WAVES_LARGE 2   /* ... teams of 6 to 8 */
-#endif
+// 2^20; the 5-agent variant spills 670 and halves.  So: two, for every team size.
+constexpr int lv_waves(int) { return 2; }
 // In-loop refresh: a wavefront tops up one env per step, and takes any env with fewer than this many twisted words left (the one
 // running lowest first).  A refresh reads and rewrites the whole 2.6 KB row whatever it twists, so the threshold sets the MT19937
 // traffic: at 352 some env always qualifies and every env comes round every 64 steps (42 B read + 39 B written per env-step,
 // profiles/r05_lanev_traffic.md); lower thresholds refresh by need.
-#ifndef CS_LV_NORMAL
-#define CS_LV_NORMAL 0   /* NORMAL = LOW + 128.  Measured A/B on one box, two passes (round 5): 3 agents 352 -> 224: 2^18 envs 21.7 -> 21.3 us
-                            per step, 65536 envs 8.3 -> 8.05; 5 agents 352 -> 288: no difference */
-#endif
-#ifndef CS_LV_BLOCK
-#define CS_LV_BLOCK 256   /* threads per workgroup of k_rollout_lanev (>= 128: load_trig_to_lds) */
-#endif
-constexpr int LV_BLOCK = CS_LV_BLOCK;
-constexpr int lv_waves(int n) { return n <= 3 ? CS_LV_WAVES_SMALL : (n <= 5 ? CS_LV_WAVES_MID : CS_LV_WAVES_LARGE); }
+// NORMAL = LOW + 128.  Measured A/B on one box, two passes (round 5): 3 agents 352 -> 224: 2^18 envs 21.7 -> 21.3 us per step,
+// 65536 envs 8.3 -> 8.05; 5 agents 352 -> 288: no difference.
+constexpr int LV_BLOCK = 256;   // threads per workgroup of k_rollout_lanev (>= 128: load_trig_to_lds)
 constexpr int LV_PIECE = 32;           // get_state rows per staging piece: half a wavefront
 constexpr int LV_SLOT_FLOATS = 4 * G * 2;   // reset hand-over: four rows of 16 (ntx, nty) pairs
 constexpr int LV_TAPE_ROWS = TAPE_DW + 3;   // hit tapes of the wavefront's 64 envs in LDS, [dword][lane]; three rows of zeros behind
@@ -452,21 +438,18 @@ __global__ __launch_bounds__(LV_BLOCK, WV) void k_rollout_lanev(DevParams p, Ste
         e.flags &= ~(FLAG_DIRTY | FLAG_RESET_PASS);
         // ---- in-loop refresh, first half: the row of the env running lowest on twisted words is requested after the kinematics
         //      and twisted after the draws of this step (each env comes round about every 64 steps)
-#ifndef CS_LV_REFRESH_EARLY
-#define CS_LV_REFRESH_EARLY 0   /* request the refresh row BEFORE the kinematics instead of after them: measured on one box, two
-                                   runs each (tools/gpu_r4_g.sh): 5 agents no difference, 3 agents -2..-3 % */
-#endif
+        //      (requesting it BEFORE the kinematics instead, measured on one box, two runs each: 5 agents no difference, 3 agents
+        //      -2..-3 %)
         RowRegs rr;
         int cand;
         auto request_row = [&]() __attribute__((always_inline)) {
-            constexpr int URGENT = LOW + 64, NORMAL = CS_LV_NORMAL > LOW + 128 ? CS_LV_NORMAL : LOW + 128;
+            constexpr int URGENT = LOW + 64, NORMAL = LOW + 128;
             const unsigned long long urgent = __ballot(e.ahead < URGENT), normal = __ballot(e.ahead < NORMAL);
             cand = urgent ? __ffsll((long long)urgent) - 1 : (normal ? __ffsll((long long)normal) - 1 : -1);
             if (cand >= 0) row_load(p.mt + (size_t)(b0 + cand) * MT_STRIDE, lane, rr);
         };
-        if (CS_LV_REFRESH_EARLY) request_row();
         if (stepping) kinematics_v<N>(p, T, act, e);
-        if (!CS_LV_REFRESH_EARLY) request_row();
+        request_row();
         LANE_STAMP(2);
         // ---- the agents' floats (get_obs / get_state)
         float fx[N], fy[N];

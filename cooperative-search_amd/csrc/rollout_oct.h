@@ -36,11 +36,9 @@
                                 4.100 -> 4.292 / 4.280 -- the one-wavefront kernel is at its 168-VGPR cap and the four extra registers cost
                                 more (22 -> 26 spilled VGPRs at 5 agents) than the eight instructions per agent save */
 #endif
-#ifndef CS_OCT_WAVES
-#define CS_OCT_WAVES 3                     /* wavefronts per SIMD the register budget must allow (168 VGPRs): measured 2 / 3 / 4,
-                                              3 agents 16384 envs 3.00 / 3.10 / 3.25 us per step, 32768: 6.04 / 5.62 / 5.58;
-                                              5 agents 16384: 4.51 / 4.63 / 4.87, 32768: 8.34 / 7.67 / 7.37 (at 4 the cold paths spill) */
-#endif
+// wavefronts per SIMD the register budget must allow (168 VGPRs): measured 2 / 3 / 4, 3 agents 16384 envs 3.00 / 3.10 / 3.25 us per
+// step, 32768: 6.04 / 5.62 / 5.58; 5 agents 16384: 4.51 / 4.63 / 4.87, 32768: 8.34 / 7.67 / 7.37 (at 4 the cold paths spill)
+constexpr int OCT_WAVES = 3;
 constexpr int OG = 8;                      // lanes per env
 constexpr int OCT_ENVS = 64 / OG;          // envs per wavefront
 constexpr int OCT_BLOCK = 256;             // 4 wavefronts = 32 envs
@@ -192,11 +190,7 @@ struct OctKin {   // one lane's agent during the kinematics of a step
 // denominator alone.  For operands whose exponents are far from the ends of the range (here: squared distances below 9, terms
 // below 3) v_div_scale scales nothing and v_div_fixup changes nothing, so the sequence below IS that expansion with the
 // reciprocal shared; anything else (never seen: a squared distance below 1e-30) takes the plain divisions.
-#ifndef CS_SHARED_RCP_DIV
-#define CS_SHARED_RCP_DIV 1
-#endif
 __device__ __forceinline__ void div2_same_denominator(double nx, double ny, double den, double &qx, double &qy) {
-#if CS_SHARED_RCP_DIV
     // the guard: den within 2^-100 .. 2^100, each numerator zero or within that range (NaN and infinities fail the <=).  The lower
     // bounds of the numerators are tested on their binary exponents (v_frexp_exp_i32_f64 gives 0 for a zero, so a zero passes): eight
     // instructions where the six range comparisons of round 4 took eighteen
@@ -212,7 +206,6 @@ __device__ __forceinline__ void div2_same_denominator(double nx, double ny, doub
         qy = __builtin_fma(__builtin_fma(-den, my, ny), r, my);
         return;
     }
-#endif
     qx = nx / den;
     qy = ny / den;
 }
@@ -299,10 +292,7 @@ __device__ __forceinline__ unsigned oct_kinematics(const DevParams &p, const dou
     const double yw = yaw, yr = (yaw <= PI) ? PI - yaw : THREE_PI - yaw;
     double s1, c1, s2, c2;
     KIN_STAMP(3);
-#ifndef CS_OCT_TRIG_SPLIT
-#define CS_OCT_TRIG_SPLIT 1   /* teams of up to 4: the wall reflection's sin / cos come from the idle lane four places up */
-#endif
-    if constexpr (CS_OCT_TRIG_SPLIT && N <= 4) {
+    if constexpr (N <= 4) {   // teams of up to 4: the wall reflection's sin / cos come from the idle lane four places up
         // Lanes 4..7 of an octet hold no agent.  Lane t + 4 evaluates agent t's REFLECTED heading while lane t evaluates the new
         // one: one correctly rounded evaluation per lane instead of two interleaved ones -- the chain is as long, but a lone
         // wavefront is bound by instruction issue (one per ~4.5 cycles), and the pair is ~100 instructions (same values: the
@@ -331,10 +321,7 @@ __device__ __forceinline__ unsigned oct_kinematics(const DevParams &p, const dou
     // one per stage (3 agents: ~3 wavefront-steps in 4); otherwise the stages run, exactly.
     // (measured, pair kernel: 3 agents -2 % per step, 5 agents +5 %: with 40 agents per wavefront some pair is nearly always
     // in range and the pre-test is pure overhead -- so only small teams take it)
-#ifndef CS_OCT_FASTPATH_MAX_N
-#define CS_OCT_FASTPATH_MAX_N 3
-#endif
-    constexpr bool FASTPATH = N <= CS_OCT_FASTPATH_MAX_N;
+    constexpr bool FASTPATH = N <= 3;
     bool any_pair = !FASTPATH;
 #pragma unroll
     for (int I = 0; I < (FASTPATH ? N : 0); I++) {
@@ -740,7 +727,7 @@ __device__ __forceinline__ void oct_place_targets(const DevParams &cp, int wave_
 }
 
 template <int N, bool VEC, bool EMIT>
-__global__ __launch_bounds__(OCT_BLOCK, CS_OCT_WAVES) void k_rollout_oct(DevParams p, StepIO io) {
+__global__ __launch_bounds__(OCT_BLOCK, OCT_WAVES) void k_rollout_oct(DevParams p, StepIO io) {
     __shared__ double T[TRIG_ROWS * TRIG_COLS];
     __shared__ OctShared shared[OCT_BLOCK / 64];
     __shared__ double rtab[4 * G];
@@ -921,7 +908,7 @@ __global__ __launch_bounds__(OCT_BLOCK, CS_OCT_WAVES) void k_rollout_oct(DevPara
         const bool stepping = live && !(done && freeze);
         OCT_STAMP(1);
         // ---- kinematics -> positions, obs floats, out flags
-        const unsigned out = oct_kinematics<N, CS_SHARED_RCP_DIV != 0>(p, T, sh.pos, o, t, sh8, stepping, act, e);
+        const unsigned out = oct_kinematics<N, true>(p, T, sh.pos, o, t, sh8, stepping, act, e);
         OCT_STAMP(2);
         if (stepping) e.flags = (e.flags & ~0xff00) | (int)(out << 8);
         sh.pos[o][t] = make_double2(e.x, e.y);

@@ -29,31 +29,19 @@
 //      every event -- no longer has to do.
 // Arithmetic per env is the octet kernel's (same functions), so results are bit-identical.
 // =========================================================================================================
-#ifndef CS_OD_WAVES
-#define CS_OD_WAVES 4
-#endif
-#ifndef CS_OD_RING
-#define CS_OD_RING 4
-#endif
-#ifndef CS_OD_RING_E3
-#define CS_OD_RING_E3 8   /* ring depth of the three-wavefront variant (measured at c2: 2 -> 2.74e9, 4 -> 3.07e9, 8 -> 3.15e9) */
-#endif
 constexpr int OD_BLOCK = 128;
+constexpr int OD_WAVES = 4;   // wavefronts per SIMD the register budget must allow
 // K divides the two components of a repulsion term with ONE reciprocal (div2_same_denominator: the same quotients bit for bit) where it
 // measured faster.  Small teams keep the plain divisions: K is alone on its SIMD there and the range check in front of the shared
 // sequence lengthens its chain (c2: -1.9 %, round 4).  The PAIR variant at 5 agents: no difference (round 5: 3.432 -> 3.438 us per step
 // at 16384 envs; round 6: 3.173 / 3.204 -> 3.203 / 3.194).  The THREE-WAVEFRONT variant at 5 agents: 1.962 -> 1.935 (round 5), 1.975 /
-// 1.981 -> 1.909 / 1.941 us per step at 8192 envs (round 6, profiles/r06_knob_sweep.log): on from teams of CS_ODE_SHARED_DIV_FROM_N.
-#ifndef CS_OD_SHARED_DIV_FROM_N
-#define CS_OD_SHARED_DIV_FROM_N 99   /* pair variant */
-#endif
-#ifndef CS_ODE_SHARED_DIV_FROM_N
-#define CS_ODE_SHARED_DIV_FROM_N 5   /* three-wavefront variant */
-#endif
+// 1.981 -> 1.909 / 1.941 us per step at 8192 envs (round 6, profiles/r06_knob_sweep.log): on from teams of ODE_SHARED_DIV_FROM_N.
+constexpr int OD_SHARED_DIV_FROM_N = 99;   // pair variant
+constexpr int ODE_SHARED_DIV_FROM_N = 5;   // three-wavefront variant
 // steps K may be ahead of D (power of two).  The pair variant serves up to 16384 envs with eight workgroups per CU: 20 KB of LDS each,
 // four slots.  The three-wavefront variant stops at 8192 envs = four workgroups per CU, so its ring can be eight deep (30 KB + E's row buffer):
-// K absorbs more of D's events before it has to wait for a slot.
-constexpr int od_ring(bool e3) { return e3 ? CS_OD_RING_E3 : CS_OD_RING; }
+// K absorbs more of D's events before it has to wait for a slot (measured at c2: 2 -> 2.74e9, 4 -> 3.07e9, 8 -> 3.15e9).
+constexpr int od_ring(bool e3) { return e3 ? 8 : 4; }
 static_assert((od_ring(false) & (od_ring(false) - 1)) == 0 && od_ring(false) >= 2, "ring depth");
 static_assert((od_ring(true) & (od_ring(true) - 1)) == 0 && od_ring(true) >= 2, "ring depth");
 
@@ -92,14 +80,11 @@ struct __attribute__((aligned(16))) OdSharedT {
     double rtab[4 * G];                      // the reset's target tables (load_reset_tab)
 };
 
-// CS_OD_E_REFRESH (three-wavefront variant): E, which has most of a step to spare, does the MT19937 row refreshes instead of D.
+// E refresh (three-wavefront variant): E, which has most of a step to spare, does the MT19937 row refreshes instead of D.
 // D posts (env, cursor, twisted words ahead) and goes on drawing from the env's old tape, which covers the words still ahead; E loads
 // the row, twists it ahead of THAT cursor (the words it writes lie behind the cursor D reads from, in ring order), computes the
 // 320-slot hit tape and posts it; D adopts it at a step boundary, shifted by the slots it consumed meanwhile.  One request at a time;
 // anything that needs the row itself (a reset, an on-the-spot top-up) first waits for the outstanding one.
-#ifndef CS_OD_E_REFRESH
-#define CS_OD_E_REFRESH 1   /* measured: c2 3.17 -> 3.30e9 at 100 steps per launch, 1.75 -> 1.79e9 at 20; c5's 8192-env shard 3.77 -> 4.00e9 */
-#endif
 template <bool ON>
 struct __attribute__((aligned(16))) OdRefreshT {
     int rf_req, rf_done;                     // D -> E: sequence number of the latest request / E -> D: ... of the latest one served
@@ -137,14 +122,6 @@ __device__ __forceinline__ int2 lds_peek2(const int *base) {
     return make_int2(v.x, v.y);
 }
 
-#ifndef CS_OD_COLD_PARAMS
-#define CS_OD_COLD_PARAMS 1
-#endif
-#if CS_OD_COLD_PARAMS
-#define OD_COLD() cold_params()
-#else
-#define OD_COLD() p
-#endif
 // E3: a THIRD wavefront per 8 envs, E, owns the get_state tile and writes every output (reward, terminated, win, obs, state) --
 // a quarter of D's plain step.  D, which also carries every reset and row top-up, is the pair's slower half (K alone sustains
 // ~3500 cycles per step, D ~2650 + ~1450 of events); without the emission it has the slack to absorb its events.  D hands each
@@ -173,7 +150,7 @@ struct __attribute__((aligned(16))) OdOutT {
 template <int N, bool VEC, bool EMIT, bool E3, int LG>
 __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO &io);
 template <int N, bool VEC, bool EMIT, bool E3>
-__global__ __launch_bounds__(E3 ? OD_BLOCK + 64 : OD_BLOCK, CS_OD_WAVES) void k_rollout_od(DevParams p, StepIO io) {
+__global__ __launch_bounds__(E3 ? OD_BLOCK + 64 : OD_BLOCK, OD_WAVES) void k_rollout_od(DevParams p, StepIO io) {
     rollout_od_body<N, VEC, EMIT, E3, OG>(p, io);
 }
 template <int N, bool VEC, bool EMIT, bool E3, int LG>
@@ -190,7 +167,7 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
     using OdOut = OdOutT<ENVS>;
     __shared__ OdShared sh;
     __shared__ OdOut outs[E3 ? OD_RING : 1];
-    constexpr bool EREF = E3 && (CS_OD_E_REFRESH != 0);
+    constexpr bool EREF = E3;   // E does D's row refreshes (OdRefreshT above)
     __shared__ OdRefreshT<EREF> rf;
     int &e_steps = sh.e_steps;
     const int lane = threadIdx.x & 63;
@@ -199,11 +176,8 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
     // wavefront 1 beside wavefront 2.  With E (busy a third of the time) in the middle, K and D -- the two full-time
     // wavefronts -- only ever share with an E.  Measured (us per step, 100-step launches, 3 agents x 4096 envs): K,E,D 1.62;
     // D,E,K 1.62; E,K,D 1.72; K,D,E 1.81; E,D,K 1.74; D,K,E 1.74.
-#ifndef CS_ODE_ROLES
-#define CS_ODE_ROLES 0x120   /* nibble w = role of wavefront w of the workgroup (0: K, 1: D, 2: E) */
-#endif
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int role = E3 ? (CS_ODE_ROLES >> (4 * wv)) & 15 : wv;   // 0: K, 1: D, 2: E
+    const int role = E3 ? (0x120 >> (4 * wv)) & 15 : wv;   // 0: K, 1: D, 2: E (E3: nibble w = role of wavefront w: K,E,D)
     const bool is_k = role == 0;
     SPIN_DECL;
     const int o = Lay::env(lane), sh8 = Lay::first(lane);
@@ -244,10 +218,7 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
         // ------------------------------------------------------------------------------------------ K: kinematics
         // with the emitting wavefront K bounds the pipeline: it wins the issue arbitration against whoever shares its SIMD
         // (an E of the neighbouring workgroup at 4096 envs, two or three other wavefronts at 8192: -2 % / -4 % per step)
-#ifndef CS_ODE_KPRIO
-#define CS_ODE_KPRIO 3
-#endif
-        if (E3) __builtin_amdgcn_s_setprio(CS_ODE_KPRIO);
+        if (E3) __builtin_amdgcn_s_setprio(3);
         {
             const double4 a = reinterpret_cast<const double4 *>(p.agent + bl * CS_MAX_AGENTS * 4)[t < CS_MAX_AGENTS ? t : 0];
             e.x = a.x;
@@ -292,11 +263,7 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             }
             const bool stepping = sel && live && !(k_done && freeze);
-#ifdef CS_OD_ABL_NOKIN   /* experiment: what D alone sustains */
-            const unsigned out = 0u;
-#else
-            const unsigned out = oct_kinematics<N, (N >= (E3 ? CS_ODE_SHARED_DIV_FROM_N : CS_OD_SHARED_DIV_FROM_N)), LG, AP>(p, T, sh.kpos, o, t, sh8, stepping, a, e, sp);
-#endif
+            const unsigned out = oct_kinematics<N, (N >= (E3 ? ODE_SHARED_DIV_FROM_N : OD_SHARED_DIV_FROM_N)), LG, AP>(p, T, sh.kpos, o, t, sh8, stepping, a, e, sp);
             KIN_STAMP_SP(6);
             between();
             if (stepping) {
@@ -398,7 +365,7 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
         }
         handle_fix(io.T);
         if (live && ag)   // agents are K's part of the state
-            reinterpret_cast<double4 *>(OD_COLD().agent + (size_t)b * CS_MAX_AGENTS * 4)[t] = make_double4(e.x, e.y, e.yaw, 0.0);
+            reinterpret_cast<double4 *>(cold_params().agent + (size_t)b * CS_MAX_AGENTS * 4)[t] = make_double4(e.x, e.y, e.yaw, 0.0);
         BLK_STAMP(3);
         return;
     }
@@ -440,13 +407,13 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             const int g = __builtin_amdgcn_readfirstlane(rf.rf_env), pos = __builtin_amdgcn_readfirstlane(rf.rf_pos);
             const int a = __builtin_amdgcn_readfirstlane(rf.rf_ahead);
-            unsigned *m = OD_COLD().mt + (size_t)(wave_b0 + g) * MT_STRIDE;
+            unsigned *m = cold_params().mt + (size_t)(wave_b0 + g) * MT_STRIDE;
             RowRegs rr;
             row_load(m, lane, rr);
             row_to_lds(rr, rf.erow, lane);
             row_twist_ahead(rf.erow, m, pos, a < 0 ? 0 : a, lane);
             unsigned long long bms[TAPE_DW / 2];
-            row_hits_all(OD_COLD(), rf.erow, pos, lane, bms);
+            row_hits_all(cold_params(), rf.erow, pos, lane, bms);
 #pragma unroll
             for (int it = 0; it < TAPE_DW / 2; it++) {
                 const unsigned long long bm = bms[it];
@@ -538,14 +505,9 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
     // The pair variant (two K and two D wavefronts per SIMD at 16384 envs): D ahead of K in the issue arbitration.  One box, two passes,
     // us per step at 16384 envs, priority 0 / 1 / 2 / 3: 5 agents 3.29-3.31 / 3.18 / 3.18-3.19 / 3.15-3.22, 3 agents 2.35-2.36 / 2.29-2.31 /
     // 2.30-2.34 / 2.28-2.31 (8192 envs, 3: 2.17 -> 2.08 / 1.64 -> 1.55); K at 3 instead: 3.25 / 2.38, and slower at 8192 and 32768 envs.
-#ifndef CS_OD_DPRIO
-#define CS_OD_DPRIO 1
-#endif
-    if (!E3) __builtin_amdgcn_s_setprio(CS_OD_DPRIO);
-#ifndef CS_ODE_DPRIO
-#define CS_ODE_DPRIO 2   /* three-wavefront variant: K (3) > D (2) > E (0) where wavefronts share a SIMD: -3 % per step at 8192 envs */
-#endif
-    if (E3) __builtin_amdgcn_s_setprio(CS_ODE_DPRIO);
+    if (!E3) __builtin_amdgcn_s_setprio(1);
+    // three-wavefront variant: K (3) > D (2) > E (0) where wavefronts share a SIMD: -3 % per step at 8192 envs
+    if (E3) __builtin_amdgcn_s_setprio(2);
     e.ahead = live ? p.ahead[bl] : (1 << 20);
     {
         const double2 *t2 = reinterpret_cast<const double2 *>(p.tgt + bl * G * 2);
@@ -573,11 +535,9 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
     load_trig_to_lds(T);   // (K's table; D only joins its barrier -- after which K produces ahead, up to OD_RING steps)
     unsigned tape[TAPE_DW];
     bool tape_ok = tape_finish(p, traw, e, tape) || !live;
-#ifndef CS_OD_LAZY_TAPE
-#define CS_OD_LAZY_TAPE 1   /* the step's detection pass leaves the tape unshifted (oct_detect_impl, LAZY); 0: shifted every step */
-#endif
+    // the step's detection pass leaves the tape unshifted (oct_detect_impl, LAZY)
     int tcur = 0;   // the cursor's bit within tape[0]; 0 = canonical, which everything but the step's own pass expects
-    auto canon = [&]() __attribute__((always_inline)) { if (CS_OD_LAZY_TAPE) tape_canon(tape, tcur); };
+    auto canon = [&]() __attribute__((always_inline)) { tape_canon(tape, tcur); };
     float *row = sh.tile + o * W;
     auto put_found = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -610,15 +570,11 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
 #define CS_OD_ASYNC 1   /* rows and reset words are fetched a step ahead, straight into LDS (global_load_lds: no registers; the
                            first version held the row in ten VGPRs across the step and was slower: spills in the hot path) */
 #endif
-#ifndef CS_OD_DRAIN
-#define CS_OD_DRAIN 0
-#endif
-#ifndef CS_OD_REQ_SLACK
-#define CS_OD_REQ_SLACK 64   /* words above one step's worst case at which an env's row is requested (an env that falls below LOW
-                                before its turn is topped up on the spot).  The first setting, max(LOW, 96), refreshed a 5-agent row
-                                with 300 of its 624 words still unused: every refresh costs the same ~4000 cycles whatever it twists */
-#endif
-    constexpr int REQ = CS_OD_ASYNC ? LOW + CS_OD_REQ_SLACK : 0;
+    // words above one step's worst case at which an env's row is requested (an env that falls below LOW before its turn is topped
+    // up on the spot).  The first setting, max(LOW, 96), refreshed a 5-agent row with 300 of its 624 words still unused: every
+    // refresh costs the same ~4000 cycles whatever it twists
+    constexpr int REQ_SLACK = 64;
+    constexpr int REQ = CS_OD_ASYNC ? LOW + REQ_SLACK : 0;
     // The requests of a step are issued BEFORE its output stores, and loads / stores retire in order: waiting until no more
     // than the step's own stores are in flight is waiting for the requests -- without also sitting out the stores, which were
     // issued a few hundred cycles ago and take a memory round trip (measured: a plain vmcnt(0) here cost ~1000 cycles per event).
@@ -679,7 +635,7 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
     };
     unsigned long long pre_need = 0ull;  // the reset mask sh.prebuf was filled for
     unsigned pre_valid = 0u;             // bit g: 16-lane group g's attempt batch is (on its way) in sh.prebuf
-    oct_wave_advance<N, CS_OD_DRAIN != 0, LG>(p, wave_b0, nvalid, lane, io.min_ahead > LOW ? io.min_ahead : LOW, sh.rowbuf, e, tape, tape_ok);   // while K produces step 0
+    oct_wave_advance<N, false, LG>(p, wave_b0, nvalid, lane, io.min_ahead > LOW ? io.min_ahead : LOW, sh.rowbuf, e, tape, tape_ok);   // while K produces step 0
     // ---- write-out plan (loop invariant)
     const int rows_valid = nvalid;
     const int ol = lane < rows_valid * N ? lane : rows_valid * N - 1;
@@ -702,7 +658,7 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
         if (__builtin_expect(cand >= 0, 0)) {   // wave-uniform: the row requested a step ago is in sh.rowbuf
             wait_for_requests();
             canon();
-            oct_advance_finish<N, LG>(OD_COLD(), wave_b0, cand, lane, sh.rowbuf, e, tape, tape_ok);
+            oct_advance_finish<N, LG>(cold_params(), wave_b0, cand, lane, sh.rowbuf, e, tape, tape_ok);
             cand = -1;
         }
         if (EREF) rf_poll(false);
@@ -710,7 +666,7 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
             if (EREF) rf_poll(true);   // (E may be at this very row; and its answer may be all that was needed)
             canon();
             if (!EREF || __ballot(live && e.ahead < LOW) != 0ull)
-                oct_wave_advance<N, CS_OD_DRAIN != 0, LG>(OD_COLD(), wave_b0, nvalid, lane, LOW, sh.rowbuf, e, tape, tape_ok);
+                oct_wave_advance<N, false, LG>(cold_params(), wave_b0, nvalid, lane, LOW, sh.rowbuf, e, tape, tape_ok);
         }
         bool done = e.target_find >= p.n_targets || e.time_step >= p.time_limit;
         e.flags &= ~(FLAG_DIRTY | FLAG_RESET_PASS);
@@ -721,12 +677,12 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
             DUO_STAMP(13);
             if (EREF) rf_poll(true);   // a reset tops rows up on the spot and reads stream words: not beside E's refresh
             canon();
-            const DevParams &cp = OD_COLD();
+            const DevParams &cp = cold_params();
             const bool mine = Lay::valid(lane) && ((need >> sh8) & 1ull);
             const StartTab<N> st = start_tab<N>();
             // round 0's attempt batches were requested when the envs' steps terminated (same mask -> same groups)
             // (E3: the tile still holds the rows of step s - 1 until E has written them out: the new targets wait for that)
-            oct_place_targets<N, CS_OD_DRAIN != 0, LG>(cp, wave_b0, nvalid, lane, live, need, sh.rtab, sh.tgt, sh.tile, W, sh.rowbuf, e, tape, tape_ok,
+            oct_place_targets<N, false, LG>(cp, wave_b0, nvalid, lane, live, need, sh.rtab, sh.tgt, sh.tile, W, sh.rowbuf, e, tape, tape_ok,
                                                    [&]() __attribute__((always_inline)) {
                                                        if (E3) {
                                                            while (lds_peek(&e_steps) < s) __builtin_amdgcn_s_sleep(1);
@@ -755,7 +711,7 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
                 sh.dpos[o][tc] = make_double2(sx, sy);
             }
             DUO_STAMP(14);
-            if (__ballot(live && e.ahead < LOW)) oct_wave_advance<N, CS_OD_DRAIN != 0, LG>(cp, wave_b0, nvalid, lane, LOW, sh.rowbuf, e, tape, tape_ok);
+            if (__ballot(live && e.ahead < LOW)) oct_wave_advance<N, false, LG>(cp, wave_b0, nvalid, lane, LOW, sh.rowbuf, e, tape, tape_ok);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -781,7 +737,7 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
                 e.flags |= FLAG_DIRTY;
             }
             done = done && !mine;
-            if (__ballot(live && e.ahead < LOW)) oct_wave_advance<N, CS_OD_DRAIN != 0, LG>(cp, wave_b0, nvalid, lane, LOW, sh.rowbuf, e, tape, tape_ok);
+            if (__ballot(live && e.ahead < LOW)) oct_wave_advance<N, false, LG>(cp, wave_b0, nvalid, lane, LOW, sh.rowbuf, e, tape, tape_ok);
         }
         const bool stepping = live && !(done && freeze);
         DUO_STAMP(9);
@@ -794,19 +750,12 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
         }
         // (K's progress word only grows, and a slot K published stays published -- a redo rewrites it behind fix_ack, waited for above:
         // the word is re-read only when the last value D saw does not cover step s.  With K a few steps ahead, as it is whenever D is the
-        // longer role, D's steady-state step has no LDS round trip in front of the ring read: CS_OD_KSEEN, round 6)
-#ifndef CS_OD_KSEEN
-#define CS_OD_KSEEN 1
-#endif
-        if (!CS_OD_KSEEN || k_seen <= s) {
+        // longer role, D's steady-state step has no LDS round trip in front of the ring read: round 6)
+        if (k_seen <= s) {
             while ((k_seen = peek(&sh.k_steps)) <= s) { SPIN_TICK; __builtin_amdgcn_s_sleep(1); }
         }
         OD_JITTER(7);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#ifdef CS_OD_ABL_NODET   /* experiment: what K alone sustains */
-        post(&sh.d_steps, s + 1);
-        continue;
-#endif
         const OdRing &r = sh.ring[s & (OD_RING - 1)];
         if (live) e.flags = (e.flags & ~0xff00) | (int)(r.out[o] << 8);
         // D decides the sensor tests in packed fp32 first (oct_detect_impl, PRE) -- in the PAIR variant only.  Measured (round 6, one box,
@@ -837,7 +786,7 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
-        const int reward = oct_detect_impl<N, LG, AP, CS_OD_LAZY_TAPE != 0, PRE>(p, r.pos, o, t, sh8, stepping, e, tape, tcur,
+        const int reward = oct_detect_impl<N, LG, AP, true, PRE>(p, r.pos, o, t, sh8, stepping, e, tape, tcur,
                                                                                  E3 ? &sh.dnp[o][0].x : row, E3 ? 2 : 4);
         DUO_STAMP(10);
         bool term = true, mispredicted = false;
@@ -915,7 +864,7 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
                 cand = -1;
             }
             if (__builtin_expect(cand >= 0, 0)) {
-                const unsigned *m = OD_COLD().mt + (size_t)(wave_b0 + cand) * MT_STRIDE;
+                const unsigned *m = cold_params().mt + (size_t)(wave_b0 + cand) * MT_STRIDE;
 #pragma unroll
                 for (int i = 0; i < 10; i++)   // (the tenth column reaches words 576..639: inside the row's 672, mirror included)
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(m + lane + 64 * i),
@@ -933,7 +882,7 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
                 const int ppos = __shfl(e.mt_pos, sl), pah = __shfl(e.ahead, sl);
                 const bool okg = src >= 0 && pah >= 4 * G;   // its words are twisted already: their stored values are final
                 if (okg) {
-                    const unsigned *m = OD_COLD().mt + (size_t)(wave_b0 + Lay::env_of_first(src)) * MT_STRIDE;
+                    const unsigned *m = cold_params().mt + (size_t)(wave_b0 + Lay::env_of_first(src)) * MT_STRIDE;
                     const int i0 = wrap624(ppos + 4 * t16);
 #pragma unroll
                     for (int q = 0; q < 4; q++)
@@ -987,7 +936,7 @@ __device__ __forceinline__ void rollout_od_body(const DevParams &p, const StepIO
     }
     canon();
     if (live) {   // header, cursor and tape are D's part of the state; targets were stored at each reset
-        const DevParams &cp = OD_COLD();
+        const DevParams &cp = cold_params();
         if (t == 0) {
             int4 *h4 = reinterpret_cast<int4 *>(cp.hdr + (size_t)b * CS_H_WORDS);
             h4[0] = make_int4((int)e.found, (int)e.newly, e.target_find, e.flags);

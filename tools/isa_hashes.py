@@ -28,6 +28,8 @@ def main():
                     continue
                 if cur and ln.strip() and not ln.startswith("Disassembly"):
                     body = ln.split("//")[0].strip()
+                    if body == "...":   # objdump's mark for skipped zero padding, not an instruction
+                        continue
                     body = re.sub(r"<.*?>", "", body)
                     h.update(body.encode() + b"\n")
                     n += 1
