@@ -30,6 +30,7 @@
 namespace {
 
 #include "policy_dev.h"
+#include "gru_seq.h"
 
 struct PolicyParams {
     int rows, n_agents, n_actions, obs_stride, obs_offset;  // obs row r starts at obs + r*obs_stride + obs_offset (4 floats)
@@ -405,6 +406,7 @@ __global__ __launch_bounds__(PBLOCK, 4) void k_conv_features(ConvParams p) {
 }
 
 thread_local char g_perr[200] = "";
+thread_local char g_lerr[200] = "";   // cs_gru_seq_*
 
 // persistent grid: as many blocks as the device holds at once (queried once)
 template <typename K>
@@ -524,6 +526,43 @@ int cs_policy_conv_features(const float *conv1_w_dev, const float *conv1_b_dev, 
 }
 
 const char *cs_policy_last_error(void) { return g_perr; }
+
+// ---- QMIX learner: the GRU recurrence over T steps, forward and backward in one launch each (gru_seq.h) ---------------------
+int cs_gru_seq_forward(const float *w_hh, const float *b_hh, const float *gi, const float *h0, int T, int rows, float *h_out,
+                       float *saved_out, void *stream) {
+    if (!w_hh || !b_hh || !gi || !h_out || T < 1 || rows < 1) {
+        snprintf(g_lerr, sizeof(g_lerr), "cs_gru_seq_forward: bad argument (T = %d, rows = %d; w_hh, b_hh, gi, h_out must be set)", T, rows);
+        return CS_E_ARG;
+    }
+    const GruFwdParams p{w_hh, b_hh, gi, h0, h_out, saved_out, T, rows};
+    const dim3 grid((rows + 15) / 16);
+    if (saved_out)
+        hipLaunchKernelGGL(k_gru_seq_fwd<true>, grid, dim3(GBLOCK), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(k_gru_seq_fwd<false>, grid, dim3(GBLOCK), 0, (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_lerr, sizeof(g_lerr), "cs_gru_seq_forward: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    return CS_OK;
+}
+
+int cs_gru_seq_backward(const float *w_hh, const float *dh_seq, const float *h_seq, const float *h0, const float *saved, int T,
+                        int rows, float *dgi_out, float *dgh_out, float *dh0_out, void *stream) {
+    if (!w_hh || !dh_seq || !h_seq || !saved || !dgi_out || !dgh_out || T < 1 || rows < 1) {
+        snprintf(g_lerr, sizeof(g_lerr), "cs_gru_seq_backward: bad argument (T = %d, rows = %d; only h0 and dh0_out may be null)", T, rows);
+        return CS_E_ARG;
+    }
+    const GruBwdParams p{w_hh, dh_seq, h_seq, h0, saved, dgi_out, dgh_out, dh0_out, T, rows};
+    hipLaunchKernelGGL(k_gru_seq_bwd, dim3((rows + 15) / 16), dim3(GBLOCK), 0, (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_lerr, sizeof(g_lerr), "cs_gru_seq_backward: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    return CS_OK;
+}
+
+const char *cs_learn_last_error(void) { return g_lerr; }
 
 
 }  // extern "C"

@@ -385,6 +385,40 @@ void store_episodes(const Tensor &o_tab, const Tensor &s_tab, const Tensor &u_ta
 
 int64_t abi_version() { return cs_abi_version(); }
 
+// ---- QMIX learner: the GRU recurrence over T steps (cs_gru_seq_forward / cs_gru_seq_backward) ------------------------------
+void gru_seq_forward(const Tensor &w_hh, const Tensor &b_hh, const Tensor &gi, const c10::optional<Tensor> &h0, int64_t T,
+                     int64_t rows, Tensor h_out, c10::optional<Tensor> saved_out) {
+    TORCH_CHECK(w_hh.is_cuda(), "coopsearch: w_hh must be a GPU tensor");
+    TORCH_CHECK(T >= 1 && rows >= 1, "coopsearch: T and rows must be >= 1");
+    check_f32(w_hh, "w_hh", 192 * 64, w_hh);
+    check_f32(b_hh, "b_hh", 192, w_hh);
+    check_f32(gi, "gi", T * rows * 192, w_hh);
+    if (h0.has_value() && h0->defined()) check_f32(*h0, "h0", rows * 64, w_hh);
+    check_f32(h_out, "h_out", T * rows * 64, w_hh);
+    if (saved_out.has_value() && saved_out->defined()) check_f32(*saved_out, "saved_out", T * rows * 4 * 64, w_hh);
+    const int rc = cs_gru_seq_forward(w_hh.data_ptr<float>(), b_hh.data_ptr<float>(), gi.data_ptr<float>(), opt_ptr<const float>(h0),
+                                      (int)T, (int)rows, h_out.data_ptr<float>(), opt_ptr<float>(saved_out), stream_of(w_hh));
+    TORCH_CHECK(rc == CS_OK, cs_learn_last_error());
+}
+
+void gru_seq_backward(const Tensor &w_hh, const Tensor &dh_seq, const Tensor &h_seq, const c10::optional<Tensor> &h0,
+                      const Tensor &saved, int64_t T, int64_t rows, Tensor dgi_out, Tensor dgh_out, c10::optional<Tensor> dh0_out) {
+    TORCH_CHECK(w_hh.is_cuda(), "coopsearch: w_hh must be a GPU tensor");
+    TORCH_CHECK(T >= 1 && rows >= 1, "coopsearch: T and rows must be >= 1");
+    check_f32(w_hh, "w_hh", 192 * 64, w_hh);
+    check_f32(dh_seq, "dh_seq", T * rows * 64, w_hh);
+    check_f32(h_seq, "h_seq", T * rows * 64, w_hh);
+    if (h0.has_value() && h0->defined()) check_f32(*h0, "h0", rows * 64, w_hh);
+    check_f32(saved, "saved", T * rows * 4 * 64, w_hh);
+    check_f32(dgi_out, "dgi_out", T * rows * 192, w_hh);
+    check_f32(dgh_out, "dgh_out", T * rows * 192, w_hh);
+    if (dh0_out.has_value() && dh0_out->defined()) check_f32(*dh0_out, "dh0_out", rows * 64, w_hh);
+    const int rc = cs_gru_seq_backward(w_hh.data_ptr<float>(), dh_seq.data_ptr<float>(), h_seq.data_ptr<float>(),
+                                       opt_ptr<const float>(h0), saved.data_ptr<float>(), (int)T, (int)rows, dgi_out.data_ptr<float>(),
+                                       dgh_out.data_ptr<float>(), opt_ptr<float>(dh0_out), stream_of(w_hh));
+    TORCH_CHECK(rc == CS_OK, cs_learn_last_error());
+}
+
 }  // namespace
 
 TORCH_LIBRARY(coopsearch, m) {
@@ -420,4 +454,8 @@ TORCH_LIBRARY(coopsearch, m) {
           "Tensor(g!)? obs, Tensor(h!)? state_out) -> ()", &rollout_policy_flight);
     m.def("store_episodes(Tensor o_tab, Tensor s_tab, Tensor u_tab, Tensor r_tab, Tensor term_tab, Tensor? slots, int n_actions, "
           "Tensor(a!)[] outs) -> ()", &store_episodes);
+    m.def("gru_seq_forward(Tensor w_hh, Tensor b_hh, Tensor gi, Tensor? h0, int T, int rows, Tensor(a!) h_out, "
+          "Tensor(b!)? saved_out) -> ()", &gru_seq_forward);
+    m.def("gru_seq_backward(Tensor w_hh, Tensor dh_seq, Tensor h_seq, Tensor? h0, Tensor saved, int T, int rows, "
+          "Tensor(a!) dgi_out, Tensor(b!) dgh_out, Tensor(c!)? dh0_out) -> ()", &gru_seq_backward);
 }

@@ -35,7 +35,9 @@ extern "C" {
 
 #define CS_ABI_VERSION 7   /* 2: cs_layout.ahead_off (pre-twisted MT words), cs_mt_canonical; 3: cs_layout.job_off;
                               4: cs_source_hash, CS_KERNEL_OCT; 5: CS_KERNEL_ODE; 6: cs_epsilon (exploration schedule),
-                              cs_epsilon_step, CS_KERNEL_LANEV; 7: CS_CHECK_ACTIONS, cs_has_legacy_kernels */
+                              cs_epsilon_step, CS_KERNEL_LANEV; 7: CS_CHECK_ACTIONS, cs_has_legacy_kernels;
+                              still 7: cs_gru_seq_forward, cs_gru_seq_backward, cs_learn_last_error were ADDED (no
+                              existing export or struct changed: a version-7 caller works unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
 #define CS_MAX_MAP 64
@@ -347,6 +349,30 @@ int cs_store_episodes(int B, int T, int n_agents, int n_actions, int obs_w, int 
                       const float *s_tab_dev, const int64_t *u_tab_dev, const float *r_tab_dev,
                       const uint8_t *term_tab_dev, const int64_t *slot_dev, const cs_episode_out *out, void *stream);
 const char *cs_episodes_last_error(void);
+
+/* ---- QMIX learner: the GRU recurrence of the agent network over T steps, forward and backward ---------------------
+ * Replaces the per-transition unroll of policy/qmix.py:160-182 (get_q_values) over network/base_net.py:40-46
+ * (GRUCell(64)) and autograd's walk back through it: ONE launch for all T steps of all rows, whatever T is.  The batched
+ * parts (fc1, the input projection gi = W_ih x + b_ih, fc2, the mixer, dW_hh, db_hh) stay with the caller.  Gate rows of
+ * the 192-wide tensors are ordered [r | z | n] (torch.nn.GRUCell); all tensors are float32, contiguous, on the device;
+ * rows = E * n_agents, row order free (rows never mix).  The products run on the split-fp16 matrix path of
+ * cs_policy_forward (~2e-5 against fp32 torch); the backward scales each group of 16 rows by a power of two so that its
+ * gradients keep full precision whatever their magnitude.  Results do not depend on the launch geometry: bit-identical
+ * from run to run.
+ *
+ * Forward.  gi [T][rows][192]; w_hh [192][64], b_hh [192] (rnn.weight_hh / rnn.bias_hh as they are); h0 [rows][64] or
+ * NULL (zeros, init_hidden of policy/qmix.py:184-187) -> h_out [T][rows][64] = h_1 .. h_T; saved_out [T][rows][4][64] =
+ * (r, z, n, gh_n) of every step for cs_gru_seq_backward, or NULL (no-grad forward: the target network). */
+int cs_gru_seq_forward(const float *w_hh, const float *b_hh, const float *gi, const float *h0, int T, int rows,
+                       float *h_out, float *saved_out, void *stream);
+/* Backward.  dh_seq [T][rows][64] = dloss/dh_t from the layers above (fc2) for every t; h_seq, h0, saved as produced by
+ * the forward (h0 NULL = zeros) -> dgi_out [T][rows][192] = dloss/dgi_t, dgh_out [T][rows][192] = dloss/dgh_t (gh = W_hh h +
+ * b_hh), dh0_out [rows][64] = dloss/dh0 or NULL.  dW_hh = sum_t dgh_t^T h_{t-1} and db_hh = sum_t dgh_t are left to one
+ * matrix product / sum over the T * rows rows. */
+int cs_gru_seq_backward(const float *w_hh, const float *dh_seq, const float *h_seq, const float *h0,
+                        const float *saved, int T, int rows, float *dgi_out, float *dgh_out,
+                        float *dh0_out, void *stream);
+const char *cs_learn_last_error(void);
 
 #ifdef __cplusplus
 }

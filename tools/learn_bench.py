@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""Time per QMIX learn step on one GPU: the fused learner (GRUSequence: one launch for the whole forward recurrence, one for its
+backward) against the reference's per-step unroll over the same modules (QMixLearner(unroll="torch")).
+
+Cases: flight_easy with 3 and 5 agents at E = 32, 256, 1024 sampled episodes, and flight with 3 agents at E = 32; T = 200 (the
+full episode limit, as the reference learns).  The replay buffer is filled by EpisodeCollector with random actions, batches are
+drawn by DeviceReplayBuffer.sample with a fixed generator, and each learn() is timed with HIP events after warm-up steps.
+Prints ONE JSON line.
+
+    python tools/learn_bench.py [--warmup 2] [--steps 5] [--quick] [--impl both|fused|torch]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+CASES = [("flight_easy", 3, 32), ("flight_easy", 3, 256), ("flight_easy", 3, 1024),
+         ("flight_easy", 5, 32), ("flight_easy", 5, 256), ("flight_easy", 5, 1024), ("flight", 3, 32)]
+
+
+def time_learns(learner, batches, warmup):
+    import torch
+    for b in batches[:warmup]:
+        learner.learn(b)
+    torch.cuda.synchronize()
+    ms = []
+    for b in batches[warmup:]:
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        learner.learn(b)
+        t1.record()
+        t1.synchronize()
+        ms.append(t0.elapsed_time(t1))
+    return sorted(ms)[len(ms) // 2], min(ms)
+
+
+def run_case(env_name, n, E, warmup, steps, impls=("fused", "torch")):
+    import torch
+    import cooperative_search_amd as cs
+    args = cs.make_env_args(env_name, n_agents=n)
+    B = E if env_name == "flight_easy" else 2 * E
+    env = cs.BatchedFlightEnv(args, batch=B)
+    cs.apply_env_info(args, env)
+    cs.get_mixer_args(args, seed=1)
+    rb = cs.DeviceReplayBuffer(args, B)
+    g = torch.Generator("cuda").manual_seed(3)
+    cs.EpisodeCollector(env).generate_episodes(policy=cs.random_policy(g), into=rb)
+    batches = [rb.sample(E, generator=g) for _ in range(warmup + steps)]
+    out = dict(env=env_name, n_agents=n, E=E, T=args.episode_limit)
+    for impl in impls:
+        learner = cs.QMixLearner(args, device="cuda", unroll=impl)
+        med, best = time_learns(learner, batches, warmup)
+        out[f"{impl}_ms"], out[f"{impl}_min_ms"] = round(med, 3), round(best, 3)
+        del learner
+    if len(impls) == 2:
+        out["speedup"] = round(out["torch_ms"] / out["fused_ms"], 1)
+    del rb, env, batches
+    torch.cuda.empty_cache()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--quick", action="store_true", help="only flight_easy 3 agents at E = 32")
+    ap.add_argument("--impl", choices=("both", "fused", "torch"), default="both",
+                    help="time one unroll only (e.g. under rocprofv3 --kernel-trace --stats)")
+    a = ap.parse_args()
+    import torch
+    t0 = time.time()
+    cases = CASES[:1] if a.quick else CASES
+    impls = ("fused", "torch") if a.impl == "both" else (a.impl,)
+    res = [run_case(*c, a.warmup, a.steps, impls) for c in cases]
+    print(json.dumps(dict(tool="learn_bench", device=torch.cuda.get_device_name(0), warmup=a.warmup, steps=a.steps,
+                          timer="HIP events around learn(), median of the timed steps", cases=res,
+                          wall_s=round(time.time() - t0, 1))))
+
+
+if __name__ == "__main__":
+    main()
