@@ -31,6 +31,7 @@ namespace {
 
 #include "policy_dev.h"
 #include "gru_seq.h"
+#include "returns.h"
 
 struct PolicyParams {
     int rows, n_agents, n_actions, obs_stride, obs_offset;  // obs row r starts at obs + r*obs_stride + obs_offset (4 floats)
@@ -406,7 +407,7 @@ __global__ __launch_bounds__(PBLOCK, 4) void k_conv_features(ConvParams p) {
 }
 
 thread_local char g_perr[200] = "";
-thread_local char g_lerr[200] = "";   // cs_gru_seq_*
+thread_local char g_lerr[200] = "";   // cs_gru_seq_*, cs_episode_returns
 
 // persistent grid: as many blocks as the device holds at once (queried once)
 template <typename K>
@@ -557,6 +558,26 @@ int cs_gru_seq_backward(const float *w_hh, const float *dh_seq, const float *h_s
     hipLaunchKernelGGL(k_gru_seq_bwd, dim3((rows + 15) / 16), dim3(GBLOCK), 0, (hipStream_t)stream, p);
     if (hipGetLastError() != hipSuccess) {
         snprintf(g_lerr, sizeof(g_lerr), "cs_gru_seq_backward: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    return CS_OK;
+}
+
+// ---- DOP / REINFORCE learners: the returns' backward recursion over t, one lane per episode (returns.h) --------------------
+int cs_episode_returns(const float *r, const float *terminated, const float *padded, const float *q, int E, int T, float gamma,
+                       float lambda, float *out, void *stream) {
+    if (!r || !terminated || !padded || !out || E < 1 || T < 1) {
+        snprintf(g_lerr, sizeof(g_lerr), "cs_episode_returns: bad argument (E = %d, T = %d; r, terminated, padded, out must be set)", E, T);
+        return CS_E_ARG;
+    }
+    const ReturnsParams p{r, terminated, padded, q, out, E, T, gamma, lambda};
+    const dim3 grid((E + RBLOCK - 1) / RBLOCK);
+    if (q)
+        hipLaunchKernelGGL(k_episode_returns<true>, grid, dim3(RBLOCK), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(k_episode_returns<false>, grid, dim3(RBLOCK), 0, (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_lerr, sizeof(g_lerr), "cs_episode_returns: kernel launch failed");
         return CS_E_LAUNCH;
     }
     return CS_OK;

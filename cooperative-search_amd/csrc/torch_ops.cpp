@@ -419,6 +419,22 @@ void gru_seq_backward(const Tensor &w_hh, const Tensor &dh_seq, const Tensor &h_
     TORCH_CHECK(rc == CS_OK, cs_learn_last_error());
 }
 
+// ---- DOP / REINFORCE learners: the returns' recursion over t (cs_episode_returns) -----------------------------------------
+void episode_returns(const Tensor &r, const Tensor &terminated, const Tensor &padded, const c10::optional<Tensor> &q, int64_t E,
+                     int64_t T, double gamma, double td_lambda, Tensor out) {
+    TORCH_CHECK(r.is_cuda(), "coopsearch: r must be a GPU tensor");
+    TORCH_CHECK(E >= 1 && T >= 1, "coopsearch: E and T must be >= 1");
+    check_f32(r, "r", E * T, r);
+    check_f32(terminated, "terminated", E * T, r);
+    check_f32(padded, "padded", E * T, r);
+    if (q.has_value() && q->defined()) check_f32(*q, "q", E * T, r);
+    check_f32(out, "out", E * T, r);
+    const int rc = cs_episode_returns(r.data_ptr<float>(), terminated.data_ptr<float>(), padded.data_ptr<float>(),
+                                      opt_ptr<const float>(q), (int)E, (int)T, (float)gamma, (float)td_lambda,
+                                      out.data_ptr<float>(), stream_of(r));
+    TORCH_CHECK(rc == CS_OK, cs_learn_last_error());
+}
+
 }  // namespace
 
 TORCH_LIBRARY(coopsearch, m) {
@@ -458,4 +474,6 @@ TORCH_LIBRARY(coopsearch, m) {
           "Tensor(b!)? saved_out) -> ()", &gru_seq_forward);
     m.def("gru_seq_backward(Tensor w_hh, Tensor dh_seq, Tensor h_seq, Tensor? h0, Tensor saved, int T, int rows, "
           "Tensor(a!) dgi_out, Tensor(b!) dgh_out, Tensor(c!)? dh0_out) -> ()", &gru_seq_backward);
+    m.def("episode_returns(Tensor r, Tensor terminated, Tensor padded, Tensor? q, int E, int T, float gamma, float td_lambda, "
+          "Tensor(a!) out) -> ()", &episode_returns);
 }

@@ -1,4 +1,5 @@
-"""QMIX learner on the device: the consumer of DeviceReplayBuffer.sample() (policy/qmix.py of the reference).
+"""QMIX, DOP and REINFORCE learners on the device: the consumers of DeviceReplayBuffer.sample() (policy/qmix.py, policy/dop.py,
+policy/reinforce.py of the reference).
 
 The reference's `learn` (policy/qmix.py:85-130) unrolls the agent network one transition at a time (`get_q_values`,
 :160-182): fc1 -> ReLU -> GRUCell -> fc2 for the eval and the target network on E*n rows per step, T = 200 steps, and autograd
@@ -11,6 +12,11 @@ does not depend on T, and `learn` never synchronises with the host.
 `QMixLearner(..., unroll="torch")` keeps the reference's per-step loop over the same modules as the yardstick (it also runs on
 the CPU).  Parameter names, initialisation order and saved file names are the reference's, so its checkpoints load and this
 learner's checkpoints load into the reference.
+
+`DOPLearner` and `ReinforceLearner` run their actor through the same unroll.  Their one other sequential part, the backward
+recursion over t of the returns (DOP's TD(lambda) critic target, REINFORCE's discounted return), is one HIP launch
+(`episode_returns`: cs_episode_returns, csrc/returns.h); DOP's critic, the mixers and the action-probability head run once
+over all rows in torch.
 """
 import os
 
@@ -152,6 +158,53 @@ class MixerNet(nn.Module):
         return torch.bmm(q_values, k).view(episode_num, -1, 1)
 
 
+# ---- shared by the learners ---------------------------------------------------------------------------------------------------
+
+def model_dir(args, alg):
+    """<model_dir><env>_Seed<seed>_<alg>_<n>a<targets>t(AM<agent_mode>TM<target_mode>): the reference's checkpoint directory
+    (qmix.py / dop.py / reinforce.py __init__); alg: args.alg, or this default."""
+    return (getattr(args, "model_dir", "./model/") + args.env + "_Seed" + str(args.seed) + "_" + getattr(args, "alg", alg) +
+            "_{}a{}t(AM{}TM{})".format(args.n_agents, getattr(args, "target_num", 15), getattr(args, "agent_mode", 0),
+                                      getattr(args, "target_mode", 0)))
+
+
+def soft_update(pairs, tau):
+    """target <- tau * eval + (1 - tau) * target for each (eval, target) module pair, in a few multi-tensor launches."""
+    with torch.no_grad():
+        for ev, tg in pairs:
+            e, t = list(ev.parameters()), list(tg.parameters())
+            new = torch._foreach_mul(e, tau)
+            torch._foreach_add_(new, torch._foreach_mul(t, 1 - tau))
+            torch._foreach_copy_(t, new)
+
+
+def device_batch(batch, device, max_episode_len=None):
+    """A sampled (or freshly collected) batch dict on `device`, every key cut to max_episode_len steps (what agent.py:112-122
+    does before calling learn; None = the full T)."""
+    if max_episode_len is not None:
+        batch = {k: v[:, :max_episode_len] for k, v in batch.items()}
+    return {k: torch.as_tensor(v, device=device) for k, v in batch.items()}
+
+
+def actor_inputs(args, n_agents, batch, T):
+    """_get_inputs (qmix.py:132-158; _get_actor_inputs of dop.py / reinforce.py) for all T steps at once: X, X_next
+    [T, E*n, in], row e*n + agent.  inputs = obs ++ previous one-hot action (zeros at t = 0) ++ agent id; inputs_next =
+    obs_next ++ this step's one-hot ++ id."""
+    o, o_next, u_onehot = batch["o"], batch["o_next"], batch["u_onehot"]
+    E, n = int(o.shape[0]), n_agents
+    parts, parts_next = [o], [o_next]
+    if getattr(args, "last_action", True):
+        parts.append(torch.cat([torch.zeros_like(u_onehot[:, :1]), u_onehot[:, :-1]], 1))
+        parts_next.append(u_onehot)
+    if getattr(args, "reuse_network", True):
+        ids = torch.eye(n, device=o.device, dtype=o.dtype).expand(E, T, n, n)
+        parts.append(ids)
+        parts_next.append(ids)
+    X = torch.cat(parts, 3).transpose(0, 1).reshape(T, E * n, -1)
+    X_next = torch.cat(parts_next, 3).transpose(0, 1).reshape(T, E * n, -1)
+    return X, X_next
+
+
 class QMixLearner:
     """policy/qmix.py:QMIX on the device.  args: the reference's namespace after get_mixer_args (seed, lr, optimizer, gamma,
     tau, grad_norm_clip, qmix_hidden_dim, two_hyper_layers, hyper_hidden_dim, rnn_hidden_dim) and the env fields
@@ -173,10 +226,7 @@ class QMixLearner:
         self.target_qmix_net = MixerNet(args)
         for net in (self.eval_rnn, self.target_rnn, self.eval_qmix_net, self.target_qmix_net):
             net.to(self.device)
-        self.model_dir = (getattr(args, "model_dir", "./model/") + args.env + "_Seed" + str(args.seed) + "_" +
-                          getattr(args, "alg", "qmix") + "_{}a{}t(AM{}TM{})".format(args.n_agents, getattr(args, "target_num", 15),
-                                                                                   getattr(args, "agent_mode", 0),
-                                                                                   getattr(args, "target_mode", 0)))
+        self.model_dir = model_dir(args, "qmix")
         self.target_rnn.load_state_dict(self.eval_rnn.state_dict())
         self.target_qmix_net.load_state_dict(self.eval_qmix_net.state_dict())
         self.eval_parameters = list(self.eval_qmix_net.parameters()) + list(self.eval_rnn.parameters())
@@ -196,29 +246,11 @@ class QMixLearner:
 
     def soft_update(self):
         """target <- tau * eval + (1 - tau) * target (qmix.py:78-83), the same arithmetic in a few multi-tensor launches."""
-        with torch.no_grad():
-            for ev, tg in ((self.eval_rnn, self.target_rnn), (self.eval_qmix_net, self.target_qmix_net)):
-                e, t = list(ev.parameters()), list(tg.parameters())
-                new = torch._foreach_mul(e, self.tau)
-                torch._foreach_add_(new, torch._foreach_mul(t, 1 - self.tau))
-                torch._foreach_copy_(t, new)
+        soft_update(((self.eval_rnn, self.target_rnn), (self.eval_qmix_net, self.target_qmix_net)), self.tau)
 
     def get_inputs(self, batch, T):
-        """_get_inputs (qmix.py:132-158) for all T steps at once: X, X_next [T, E*n, in], row e*n + agent.
-        inputs = obs ++ previous one-hot action (zeros at t = 0) ++ agent id; inputs_next = obs_next ++ this step's one-hot ++ id."""
-        o, o_next, u_onehot = batch["o"], batch["o_next"], batch["u_onehot"]
-        E, n = int(o.shape[0]), self.n_agents
-        parts, parts_next = [o], [o_next]
-        if getattr(self.args, "last_action", True):
-            parts.append(torch.cat([torch.zeros_like(u_onehot[:, :1]), u_onehot[:, :-1]], 1))
-            parts_next.append(u_onehot)
-        if getattr(self.args, "reuse_network", True):
-            ids = torch.eye(n, device=o.device, dtype=o.dtype).expand(E, T, n, n)
-            parts.append(ids)
-            parts_next.append(ids)
-        X = torch.cat(parts, 3).transpose(0, 1).reshape(T, E * n, -1)
-        X_next = torch.cat(parts_next, 3).transpose(0, 1).reshape(T, E * n, -1)
-        return X, X_next
+        """_get_inputs (qmix.py:132-158) for all T steps at once: X, X_next [T, E*n, in], row e*n + agent (actor_inputs)."""
+        return actor_inputs(self.args, self.n_agents, batch, T)
 
     def get_q_values(self, batch, T):
         """(q_evals, q_targets) [E, T, n, n_actions] (qmix.py:160-182); the target network runs without a graph."""
@@ -236,9 +268,7 @@ class QMixLearner:
         long).  max_episode_len: cut every key to that many steps (what agent.py:112-122 does before calling learn); None = the
         full T, which is what the reference's _get_max_episode_len amounts to (it never shortens T).  Returns the loss (a device
         tensor: no host synchronisation)."""
-        if max_episode_len is not None:
-            batch = {k: v[:, :max_episode_len] for k, v in batch.items()}
-        batch = {k: torch.as_tensor(v, device=self.device) for k, v in batch.items()}
+        batch = device_batch(batch, self.device, max_episode_len)
         T = int(batch["o"].shape[1])
         u = batch["u"].long()
         s, s_next, r = batch["s"].float(), batch["s_next"].float(), batch["r"].float()
@@ -277,3 +307,323 @@ class QMixLearner:
         self.eval_qmix_net.load_state_dict(torch.load(qmix_root, map_location=self.device))
         self.target_rnn.load_state_dict(self.eval_rnn.state_dict())
         self.target_qmix_net.load_state_dict(self.eval_qmix_net.state_dict())
+
+
+# ---- DOP and REINFORCE (policy/dop.py, policy/reinforce.py) -------------------------------------------------------------------
+
+def get_dop_args(args, seed=None):
+    """The learner fields of the reference's get_dop_args (common/arguments.py:112-169) on an argparse-style namespace; seed:
+    args.seed (the reference draws one when training; here the caller chooses)."""
+    args.off_policy = True
+    args.rnn_hidden_dim, args.offpg_hidden_dim, args.qmix_hidden_dim = 64, 128, 32
+    args.two_hyper_layers, args.hyper_hidden_dim = False, 64
+    args.lr, args.critic_lr, args.td_lambda, args.tau = 5e-4, 1e-4, 0.8, 0.05
+    args.gamma, args.optimizer = getattr(args, "gamma", 0.99), getattr(args, "optimizer", "Adam")
+    args.epsilon, args.min_epsilon, args.epsilon_anneal_scale = 1, 0.05, "step"
+    args.anneal_epsilon = (args.epsilon - args.min_epsilon) / 10000
+    args.n_epoch, args.n_episodes, args.train_steps, args.evaluate_cycle = 500000, 1, 1, 200
+    args.batch_size, args.buffer_size, args.onbuffer_size = 32, 3000, 32
+    args.save_cycle, args.target_update_cycle, args.grad_norm_clip = 500, 200, 10
+    if seed is not None:
+        args.seed = seed
+    return args
+
+
+def get_reinforce_args(args, seed=None):
+    """The learner fields of the reference's get_reinforce_args (common/arguments.py:172-216); seed as get_dop_args."""
+    args.off_policy = False
+    args.rnn_hidden_dim, args.critic_dim = 64, 128
+    args.tau, args.lr_actor, args.lr_critic = 0.05, 1e-4, 1e-3
+    args.gamma, args.optimizer = getattr(args, "gamma", 0.99), getattr(args, "optimizer", "Adam")
+    args.epsilon, args.anneal_epsilon, args.min_epsilon, args.epsilon_anneal_scale = 0.5, 0.00064, 0.02, "epoch"
+    args.batch_size, args.buffer_size = 32, 1000
+    args.n_epoch, args.n_episodes, args.evaluate_cycle, args.save_cycle = 100000, 1, 200, 500
+    args.grad_norm_clip = 10
+    if seed is not None:
+        args.seed = seed
+    return args
+
+
+class OffPGCritic(nn.Module):
+    """network/offpg_net.py with its parameter names: relu(fc1) -> relu(fc2) -> q = fc3(x) + fc_v(x), one q per action."""
+
+    def __init__(self, input_shape, args):
+        super().__init__()
+        self.args = args
+        self.input_shape = input_shape
+        self.fc1 = nn.Linear(input_shape, args.offpg_hidden_dim)
+        self.fc2 = nn.Linear(args.offpg_hidden_dim, args.offpg_hidden_dim)
+        self.fc_v = nn.Linear(args.offpg_hidden_dim, 1)
+        self.fc3 = nn.Linear(args.offpg_hidden_dim, args.n_actions)
+
+    def forward(self, inputs):
+        x = F.relu(self.fc2(F.relu(self.fc1(inputs))))
+        return self.fc3(x) + self.fc_v(x)
+
+
+def _make_optimizer(args, params, lr):
+    opt = getattr(args, "optimizer", "Adam")
+    if opt == "RMS":
+        return torch.optim.RMSprop(params, lr=lr)
+    if opt == "Adam":
+        return torch.optim.Adam(params, lr=lr)
+    raise ValueError("No such optimizer")
+
+
+def action_prob(logits, avail_u, epsilon):
+    """The action probabilities of the policy-gradient actors (_get_actor_output, dop.py:238-267 = _get_action_prob,
+    reinforce.py:131-156): softmax over the actions, the epsilon mix over the available ones, unavailable actions zeroed,
+    renormalised and zeroed again.  logits, avail_u [E, T, n, A]; epsilon: a float or a 0-dim device tensor.
+    A padded step has no available action: its row is inf / 0 = NaN after the mix and the renormalisation, as in the
+    reference, and ends as zeros.  The zeroing is masked_fill (boolean-index assignment would synchronise), whose backward
+    also zeroes the NaN that the 0 / 0 of those rows sends back, so every gradient stays finite."""
+    prob = F.softmax(logits, dim=-1)
+    unavail = avail_u == 0
+    action_num = avail_u.sum(dim=-1, keepdim=True).float()   # broadcast over the actions (the reference's repeat)
+    p = (1 - epsilon) * prob + torch.ones_like(prob) * epsilon / action_num
+    p = p.masked_fill(unavail, 0.0)
+    p = p / p.sum(dim=-1, keepdim=True)
+    return p.masked_fill(unavail, 0.0)
+
+
+def log_pi_taken(prob, u, mask):
+    """log pi(u) [E, T, n]; padded steps (mask == 0) read 1, so their log is 0 (dop.py:120-123, reinforce.py:82-84)."""
+    pi = torch.gather(prob, dim=3, index=u).squeeze(3)
+    return torch.log(pi.masked_fill(mask == 0, 1.0))
+
+
+def episode_returns(r, terminated, padded, q=None, gamma=0.99, td_lambda=0.8):
+    """cs_episode_returns (csrc/returns.h) on device tensors: r, terminated, padded (and q) [E, T] or [E, T, 1] float32 ->
+    [E, T].  q None: REINFORCE's discounted return (reinforce.py:101-110); q = q_total_target: DOP's TD(lambda) target
+    (dop.py:192-232).  One launch, whatever E and T."""
+    E, T = int(r.shape[0]), int(r.shape[1])
+    flat = lambda x: x.detach().float().reshape(E, T).contiguous()
+    out = torch.empty(E, T, dtype=torch.float32, device=r.device)
+    _ops().episode_returns(flat(r), flat(terminated), flat(padded), None if q is None else flat(q), E, T, float(gamma),
+                           float(td_lambda), out)
+    return out
+
+
+def returns_torch(r, terminated, padded, gamma):
+    """REINFORCE's _get_returns (reinforce.py:101-110) as the reference computes it: one step at a time, t = T-1 .. 0 ->
+    [E, T]."""
+    r, m, c = r.reshape(r.shape[0], -1), (1 - padded).reshape(r.shape[0], -1), (1 - terminated).reshape(r.shape[0], -1)
+    R = torch.zeros_like(r)
+    R[:, -1] = r[:, -1] * m[:, -1]
+    for t in range(r.shape[1] - 2, -1, -1):
+        R[:, t] = (r[:, t] + gamma * R[:, t + 1] * c[:, t]) * m[:, t]
+    return R
+
+
+def td_lambda_torch(r, terminated, padded, q, gamma, td_lambda):
+    """DOP's _td_lambda_target (dop.py:192-232) as the reference computes it, on the CPU: the [E, T, T] table of n-step
+    returns (entry [:, t, k] = the (k+1)-step return of step t) filled step by step, then the lambda-weighted sum of each row
+    in a second loop -- ~T^2 small tensor ops -> [E, T] on q's device.  (The reference repeats every row over the agents
+    first; the n columns are identical, so one is computed.)"""
+    dev = q.device
+    E, T = int(r.shape[0]), int(r.shape[1])
+    r, m, c, q = (x.detach().float().reshape(E, T).cpu() for x in (r, 1 - padded, 1 - terminated, q))
+    nstep = torch.zeros(E, T, T)
+    for t in range(T - 1, -1, -1):
+        nstep[:, t, 0] = (r[:, t] + gamma * q[:, t] * c[:, t]) * m[:, t]
+        for k in range(1, T - t):
+            nstep[:, t, k] = (r[:, t] + gamma * nstep[:, t + 1, k - 1]) * m[:, t]
+    out = torch.zeros(E, T)
+    for t in range(T):
+        acc = torch.zeros(E)
+        for k in range(1, T - t):
+            acc += pow(td_lambda, k - 1) * nstep[:, t, k - 1]
+        out[:, t] = (1 - td_lambda) * acc + pow(td_lambda, T - t - 1) * nstep[:, t, T - t - 1]
+    return out.to(dev)
+
+
+def _policy_logits(net, args, n_agents, batch, T, impl):
+    """The actor's outputs [E, T, n, A] over all T steps: actor_inputs' X through unroll_q (the fused recurrence, or the
+    reference's step loop)."""
+    E = int(batch["o"].shape[0])
+    X, _ = actor_inputs(args, n_agents, batch, T)
+    return unroll_q(net, X, None, impl).view(T, E, n_agents, -1).transpose(0, 1)
+
+
+def _prepare(batch, device, max_episode_len):
+    """device_batch, then the reference's conversion (u -> long, everything else float32) -> (batch, T, u, mask [E, T, 1])."""
+    batch = device_batch(batch, device, max_episode_len)
+    batch = {k: (v.long() if k == "u" else v.float()) for k, v in batch.items()}
+    return batch, int(batch["o"].shape[1]), batch["u"], 1 - batch["padded"]
+
+
+class DOPLearner:
+    """policy/dop.py:DOP on the device.  args: the reference's namespace after get_dop_args (seed, lr, critic_lr, td_lambda,
+    optimizer, gamma, tau, grad_norm_clip, offpg_hidden_dim, qmix_hidden_dim, two_hyper_layers, hyper_hidden_dim,
+    rnn_hidden_dim) and the env fields (apply_env_info).  unroll: "fused" (the critic over all T*E*n rows at once, the actor
+    through GRUSequence, the TD(lambda) target from cs_episode_returns; needs the HIP library and a GPU) or "torch" (the
+    reference's per-transition loops and its O(T^2) lambda-return, over the same modules; also runs on the CPU)."""
+
+    def __init__(self, args, device="cuda", unroll="fused"):
+        if unroll not in ("fused", "torch"):
+            raise ValueError("unroll must be 'fused' or 'torch'")
+        self.args, self.device, self.unroll = args, torch.device(device), unroll
+        self.n_actions, self.n_agents = args.n_actions, args.n_agents
+        self.state_shape, self.obs_shape = args.state_shape, args.obs_shape
+        self.tau = args.tau
+        # s ++ o ++ agent id (dop.py:25).  flight's o also carries the probability map (conv): the critic reads it as it is
+        # (the reference counts obs_shape only, so its critic cannot take flight's observations)
+        obs_width = self.obs_shape + (args.map_size ** 2 if getattr(args, "conv", False) else 0)
+        critic_input_shape = self.state_shape + obs_width + self.n_agents
+        # the reference's order (dop.py:30-47): seed, then actor, eval / target critic, eval / target mixer, on the CPU
+        torch.manual_seed(args.seed)
+        self.actor = AgentRNN(rnn_input_shape(args), args)
+        self.eval_critic = OffPGCritic(critic_input_shape, args)
+        self.target_critic = OffPGCritic(critic_input_shape, args)
+        self.eval_mixer_net = MixerNet(args)
+        self.target_mixer_net = MixerNet(args)
+        for net in (self.actor, self.eval_critic, self.target_critic, self.eval_mixer_net, self.target_mixer_net):
+            net.to(self.device)
+        self.model_dir = model_dir(args, "dop")
+        self.target_critic.load_state_dict(self.eval_critic.state_dict())
+        self.target_mixer_net.load_state_dict(self.eval_mixer_net.state_dict())
+        self.actor_params = list(self.actor.parameters())
+        self.critic_params = list(self.eval_critic.parameters())
+        self.mixer_params = list(self.eval_mixer_net.parameters())
+        self.c_params = self.critic_params + self.mixer_params
+        self.agent_optimizer = _make_optimizer(args, self.actor_params, args.lr)
+        self.critic_optimizer = _make_optimizer(args, self.critic_params, args.critic_lr)
+        self.mixer_optimizer = _make_optimizer(args, self.mixer_params, args.critic_lr)
+        self.last_critic_grad_norm = self.last_actor_grad_norm = None
+
+    def soft_update(self):
+        """dop.py:132-136: critic and mixer only (the actor has no target)."""
+        soft_update(((self.eval_critic, self.target_critic), (self.eval_mixer_net, self.target_mixer_net)), self.tau)
+
+    def critic_inputs(self, batch):
+        """_get_critic_inputs (dop.py:269-310) for all steps: s ++ o ++ agent id and s_next ++ o_next ++ id, [E, T, n, in]."""
+        o = batch["o"]
+        E, T, n = int(o.shape[0]), int(o.shape[1]), self.n_agents
+        ids = torch.eye(n, device=o.device, dtype=o.dtype).expand(E, T, n, n)
+        s, s_next = (batch[k].unsqueeze(2).expand(E, T, n, self.state_shape) for k in ("s", "s_next"))
+        return torch.cat([s, o, ids], 3), torch.cat([s_next, batch["o_next"], ids], 3)
+
+    def critic_q(self, batch):
+        """(q_evals, q_targets) [E, T, n, A] (_get_q_values, dop.py:312-335); the target critic runs without a graph."""
+        X, X_next = self.critic_inputs(batch)
+        if self.unroll == "fused":
+            q_eval = self.eval_critic(X)
+            with torch.no_grad():
+                q_target = self.target_critic(X_next)
+            return q_eval, q_target
+        E, T, n = X.shape[:3]
+        q_eval = torch.stack([self.eval_critic(X[:, t].reshape(E * n, -1)).view(E, n, -1) for t in range(T)], 1)
+        with torch.no_grad():
+            q_target = torch.stack([self.target_critic(X_next[:, t].reshape(E * n, -1)).view(E, n, -1) for t in range(T)], 1)
+        return q_eval, q_target
+
+    def td_lambda_target(self, batch, q_total_target):
+        """[E, T] TD(lambda) target of the critic (dop.py:192-232)."""
+        a = self.args
+        if self.unroll == "fused":
+            return episode_returns(batch["r"], batch["terminated"], batch["padded"], q_total_target, a.gamma, a.td_lambda)
+        return td_lambda_torch(batch["r"], batch["terminated"], batch["padded"], q_total_target, a.gamma, a.td_lambda)
+
+    def learn(self, batch, max_episode_len=None, train_step=0, epsilon=0.0):
+        """One DOP update (dop.py:89-130) on a DeviceReplayBuffer.sample() dict as it is: the critic and mixer step (its TD(lambda)
+        loss, one clip over both, soft update), then the actor step with the advantage of the critic's q-values from BEFORE its
+        step (dop.py:161).  max_episode_len: as QMixLearner.learn; epsilon: a float or a 0-dim device tensor.  Returns
+        (critic_loss, actor_loss) as device tensors (no host synchronisation); the pre-clip norms are last_critic_grad_norm and
+        last_actor_grad_norm."""
+        batch, T, u, mask1 = _prepare(batch, self.device, max_episode_len)
+        E, n = int(u.shape[0]), self.n_agents
+        mask = mask1.expand(E, T, n)
+        s, s_next = batch["s"], batch["s_next"]
+
+        # critic (_train_critic, dop.py:138-190)
+        u_next = torch.cat([u[:, 1:], torch.zeros_like(u[:, :1])], 1)   # zero action after the last step (dop.py:146-148)
+        q_evals, q_targets = self.critic_q(batch)
+        q_values = q_evals.detach()
+        q_total_eval = self.eval_mixer_net(torch.gather(q_evals, dim=3, index=u).squeeze(3), s)
+        with torch.no_grad():
+            q_total_target = self.target_mixer_net(torch.gather(q_targets, dim=3, index=u_next).squeeze(3), s_next)
+        targets = self.td_lambda_target(batch, q_total_target).unsqueeze(2).expand(E, T, n)   # the reference's repeat
+        td_error = targets - q_total_eval
+        critic_loss = ((mask * td_error) ** 2).sum() / mask.sum()
+        self.critic_optimizer.zero_grad()
+        self.mixer_optimizer.zero_grad()
+        critic_loss.backward()
+        self.last_critic_grad_norm = torch.nn.utils.clip_grad_norm_(self.c_params, self.args.grad_norm_clip)
+        self.critic_optimizer.step()
+        self.mixer_optimizer.step()
+        self.soft_update()
+
+        # actor (dop.py:107-130)
+        prob = action_prob(_policy_logits(self.actor, self.args, n, batch, T, self.unroll), batch["avail_u"], epsilon)
+        q_taken = torch.gather(q_values, dim=3, index=u).squeeze(3)
+        baseline = (q_values * prob).sum(dim=3, keepdim=True).squeeze(3).detach()
+        advantage = (q_taken - baseline).detach()
+        actor_loss = -((advantage * log_pi_taken(prob, u, mask)) * mask).sum() / mask.sum()
+        self.agent_optimizer.zero_grad()
+        actor_loss.backward()
+        self.last_actor_grad_norm = torch.nn.utils.clip_grad_norm_(self.actor_params, self.args.grad_norm_clip)
+        self.agent_optimizer.step()
+        return critic_loss.detach(), actor_loss.detach()
+
+    def save_model(self, num):
+        """dop.py:341-350: <model_dir>/<num>_actor_net_params.pkl, <num>_mixer_net_params.pkl, <num>_critic_net_params.pkl."""
+        os.makedirs(self.model_dir, exist_ok=True)
+        idx = str(num)
+        torch.save(self.actor.state_dict(), os.path.join(self.model_dir, idx + "_actor_net_params.pkl"))
+        torch.save(self.eval_mixer_net.state_dict(), os.path.join(self.model_dir, idx + "_mixer_net_params.pkl"))
+        torch.save(self.eval_critic.state_dict(), os.path.join(self.model_dir, idx + "_critic_net_params.pkl"))
+
+    def load_model(self, actor_root, critic_root, mixer_root):
+        """dop.py:352-357: actor, eval critic and eval mixer from the three files, targets copied from them."""
+        self.actor.load_state_dict(torch.load(actor_root, map_location=self.device))
+        self.eval_critic.load_state_dict(torch.load(critic_root, map_location=self.device))
+        self.eval_mixer_net.load_state_dict(torch.load(mixer_root, map_location=self.device))
+        self.target_critic.load_state_dict(self.eval_critic.state_dict())
+        self.target_mixer_net.load_state_dict(self.eval_mixer_net.state_dict())
+
+
+class ReinforceLearner:
+    """policy/reinforce.py:Reinforce on the device.  args: the reference's namespace after get_reinforce_args (seed, lr_actor,
+    optimizer, gamma, rnn_hidden_dim) and the env fields.  On-policy: `learn` takes the episode dict that
+    EpisodeCollector.generate_episodes returns (or a sampled batch).  unroll: "fused" (GRUSequence and cs_episode_returns) or
+    "torch" (the reference's step loops)."""
+
+    def __init__(self, args, device="cuda", unroll="fused"):
+        if unroll not in ("fused", "torch"):
+            raise ValueError("unroll must be 'fused' or 'torch'")
+        self.args, self.device, self.unroll = args, torch.device(device), unroll
+        self.n_actions, self.n_agents = args.n_actions, args.n_agents
+        self.state_shape, self.obs_shape = args.state_shape, args.obs_shape
+        torch.manual_seed(args.seed)   # reinforce.py:22-31
+        self.eval_rnn = AgentRNN(rnn_input_shape(args), args).to(self.device)
+        self.model_dir = model_dir(args, "reinforce")
+        self.rnn_parameters = list(self.eval_rnn.parameters())
+        self.rnn_optimizer = _make_optimizer(args, self.rnn_parameters, args.lr_actor)
+
+    def get_returns(self, batch):
+        """[E, T] discounted return of every step (_get_returns, reinforce.py:101-110)."""
+        if self.unroll == "fused":
+            return episode_returns(batch["r"], batch["terminated"], batch["padded"], None, self.args.gamma)
+        return returns_torch(batch["r"], batch["terminated"], batch["padded"], self.args.gamma)
+
+    def learn(self, batch, max_episode_len=None, train_step=0, epsilon=0.0):
+        """One REINFORCE update (reinforce.py:63-99): loss = -sum(R log pi(u) m) / sum(m), Adam or RMSprop, no gradient clipping
+        (reinforce.py:97 has it commented out).  Returns the loss as a device tensor (no host synchronisation)."""
+        batch, T, u, mask1 = _prepare(batch, self.device, max_episode_len)
+        E, n = int(u.shape[0]), self.n_agents
+        mask = mask1.expand(E, T, n)
+        n_return = self.get_returns(batch).unsqueeze(2).expand(E, T, n)
+        prob = action_prob(_policy_logits(self.eval_rnn, self.args, n, batch, T, self.unroll), batch["avail_u"], epsilon)
+        loss = -((n_return * log_pi_taken(prob, u, mask)) * mask).sum() / mask.sum()
+        self.rnn_optimizer.zero_grad()
+        loss.backward()
+        self.rnn_optimizer.step()
+        return loss.detach()
+
+    def save_model(self, num):
+        """<model_dir>/<num>_rnn_net_params.pkl, the reference's file (reinforce.py:158-164 numbers it itself)."""
+        os.makedirs(self.model_dir, exist_ok=True)
+        torch.save(self.eval_rnn.state_dict(), os.path.join(self.model_dir, str(num) + "_rnn_net_params.pkl"))
+
+    def load_model(self, rnn_root):
+        self.eval_rnn.load_state_dict(torch.load(rnn_root, map_location=self.device))

@@ -36,8 +36,9 @@ extern "C" {
 #define CS_ABI_VERSION 7   /* 2: cs_layout.ahead_off (pre-twisted MT words), cs_mt_canonical; 3: cs_layout.job_off;
                               4: cs_source_hash, CS_KERNEL_OCT; 5: CS_KERNEL_ODE; 6: cs_epsilon (exploration schedule),
                               cs_epsilon_step, CS_KERNEL_LANEV; 7: CS_CHECK_ACTIONS, cs_has_legacy_kernels;
-                              still 7: cs_gru_seq_forward, cs_gru_seq_backward, cs_learn_last_error were ADDED (no
-                              existing export or struct changed: a version-7 caller works unchanged) */
+                              still 7: cs_gru_seq_forward, cs_gru_seq_backward, cs_learn_last_error were ADDED, then
+                              cs_episode_returns (no existing export or struct changed: a version-7 caller works
+                              unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
 #define CS_MAX_MAP 64
@@ -372,6 +373,17 @@ int cs_gru_seq_forward(const float *w_hh, const float *b_hh, const float *gi, co
 int cs_gru_seq_backward(const float *w_hh, const float *dh_seq, const float *h_seq, const float *h0,
                         const float *saved, int T, int rows, float *dgi_out, float *dgh_out,
                         float *dh0_out, void *stream);
+/* DOP / REINFORCE learners: the backward recursion over t of the returns, ONE launch for all E episodes and T steps.
+ * r, terminated, padded [E][T] (the batch's [E][T][1] float32 tensors); q [E][T] = q_total_target of the target mixer, or
+ * NULL.  With m = 1 - padded, c = 1 - terminated:
+ *   q == NULL: out = REINFORCE's discounted return (policy/reinforce.py:101-110)
+ *              R[T-1] = r m,  R[t] = (r[t] + gamma R[t+1] c[t]) m[t]
+ *   q != NULL: out = DOP's TD(lambda) target (policy/dop.py:192-232, its O(T^2) n-step sum as a recursion)
+ *              L[T-1] = (r + gamma q c) m,  L[t] = (r[t] + gamma ((1 - lambda) c[t] q[t] + lambda L[t+1])) m[t]
+ * fp32 in the evaluation order stated in csrc/returns.h (no fused multiply-adds: a float32 restatement of that order is
+ * bit-identical); no atomics, so reruns are bit-identical.  lambda is ignored when q is NULL. */
+int cs_episode_returns(const float *r, const float *terminated, const float *padded, const float *q, int E, int T,
+                       float gamma, float lambda, float *out, void *stream);
 const char *cs_learn_last_error(void);
 
 #ifdef __cplusplus

@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
-"""Time per QMIX learn step on one GPU: the fused learner (GRUSequence: one launch for the whole forward recurrence, one for its
-backward) against the reference's per-step unroll over the same modules (QMixLearner(unroll="torch")).
+"""Time per learn step on one GPU: the fused learner (GRUSequence: one launch for the whole forward recurrence, one for its
+backward; for DOP and REINFORCE also one cs_episode_returns launch for the returns) against the reference's per-step unroll over
+the same modules (unroll="torch"; for DOP it includes the reference's O(T^2) lambda-return).  --alg: qmix (QMixLearner, the
+default), dop (DOPLearner) or reinforce (ReinforceLearner, here on sampled batches).
 
 Cases: flight_easy with 3 and 5 agents at E = 32, 256, 1024 sampled episodes, and flight with 3 agents at E = 32; T = 200 (the
 full episode limit, as the reference learns).  The replay buffer is filled by EpisodeCollector with random actions, batches are
 drawn by DeviceReplayBuffer.sample with a fixed generator, and each learn() is timed with HIP events after warm-up steps.
 Prints ONE JSON line.
 
-    python tools/learn_bench.py [--warmup 2] [--steps 5] [--quick] [--impl both|fused|torch]
+    python tools/learn_bench.py [--alg qmix|dop|reinforce] [--warmup 2] [--steps 5] [--quick] [--impl both|fused|torch]
+                                [--max-episode-len N]
 """
 import argparse
 import json
@@ -22,38 +25,43 @@ CASES = [("flight_easy", 3, 32), ("flight_easy", 3, 256), ("flight_easy", 3, 102
          ("flight_easy", 5, 32), ("flight_easy", 5, 256), ("flight_easy", 5, 1024), ("flight", 3, 32)]
 
 
-def time_learns(learner, batches, warmup):
+ALGS = {"qmix": ("QMixLearner", "get_mixer_args"), "dop": ("DOPLearner", "get_dop_args"),
+        "reinforce": ("ReinforceLearner", "get_reinforce_args")}
+
+
+def time_learns(learner, batches, warmup, max_episode_len=None):
     import torch
     for b in batches[:warmup]:
-        learner.learn(b)
+        learner.learn(b, max_episode_len)
     torch.cuda.synchronize()
     ms = []
     for b in batches[warmup:]:
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0.record()
-        learner.learn(b)
+        learner.learn(b, max_episode_len)
         t1.record()
         t1.synchronize()
         ms.append(t0.elapsed_time(t1))
     return sorted(ms)[len(ms) // 2], min(ms)
 
 
-def run_case(env_name, n, E, warmup, steps, impls=("fused", "torch")):
+def run_case(env_name, n, E, warmup, steps, impls=("fused", "torch"), alg="qmix", max_episode_len=None):
     import torch
     import cooperative_search_amd as cs
+    learner_cls, args_fn = (getattr(cs, name) for name in ALGS[alg])
     args = cs.make_env_args(env_name, n_agents=n)
     B = E if env_name == "flight_easy" else 2 * E
     env = cs.BatchedFlightEnv(args, batch=B)
     cs.apply_env_info(args, env)
-    cs.get_mixer_args(args, seed=1)
+    args_fn(args, seed=1)
     rb = cs.DeviceReplayBuffer(args, B)
     g = torch.Generator("cuda").manual_seed(3)
     cs.EpisodeCollector(env).generate_episodes(policy=cs.random_policy(g), into=rb)
     batches = [rb.sample(E, generator=g) for _ in range(warmup + steps)]
-    out = dict(env=env_name, n_agents=n, E=E, T=args.episode_limit)
+    out = dict(env=env_name, n_agents=n, E=E, T=min(args.episode_limit, max_episode_len or args.episode_limit))
     for impl in impls:
-        learner = cs.QMixLearner(args, device="cuda", unroll=impl)
-        med, best = time_learns(learner, batches, warmup)
+        learner = learner_cls(args, device="cuda", unroll=impl)
+        med, best = time_learns(learner, batches, warmup, max_episode_len)
         out[f"{impl}_ms"], out[f"{impl}_min_ms"] = round(med, 3), round(best, 3)
         del learner
     if len(impls) == 2:
@@ -70,13 +78,18 @@ def main():
     ap.add_argument("--quick", action="store_true", help="only flight_easy 3 agents at E = 32")
     ap.add_argument("--impl", choices=("both", "fused", "torch"), default="both",
                     help="time one unroll only (e.g. under rocprofv3 --kernel-trace --stats)")
+    ap.add_argument("--alg", choices=tuple(ALGS), default="qmix")
+    ap.add_argument("--max-episode-len", type=int, default=None, help="learn on the first N steps of every batch")
     a = ap.parse_args()
     import torch
     t0 = time.time()
     cases = CASES[:1] if a.quick else CASES
     impls = ("fused", "torch") if a.impl == "both" else (a.impl,)
-    res = [run_case(*c, a.warmup, a.steps, impls) for c in cases]
-    print(json.dumps(dict(tool="learn_bench", device=torch.cuda.get_device_name(0), warmup=a.warmup, steps=a.steps,
+    res = [run_case(*c, a.warmup, a.steps, impls, a.alg, a.max_episode_len) for c in cases]
+    head = dict(tool="learn_bench")
+    if a.alg != "qmix":   # the default keeps its output as it was
+        head["alg"] = a.alg
+    print(json.dumps(dict(head, device=torch.cuda.get_device_name(0), warmup=a.warmup, steps=a.steps,
                           timer="HIP events around learn(), median of the timed steps", cases=res,
                           wall_s=round(time.time() - t0, 1))))
 
