@@ -104,7 +104,7 @@ class FusedAgents:
     one-hot(agent id) -> fc1 -> GRUCell -> fc2 -> argmax / epsilon-greedy in ONE launch (`cs_policy_forward`, fp32 on the
     matrix cores); for flight's conv network one more launch computes the 16 conv features of every env's probability map
     (`cs_policy_conv_features`, once per env: all its agents observe the same map).  Same parameters as `AgentRNN` (the
-    reference's state_dict loads into `net`, then `load_weights()` repacks them).  Requires last_action and
+    reference's state_dict loads into `net`, then `load_weights()` repacks them on the host, `sync_weights()` on the device).  Requires last_action and
     reuse_network (the reference's defaults, common/arguments.py:52-53), the reference's conv hyper-parameters
     (:256-265) and no availability mask (every action is always available in this env, flight_env_easy.py:184-188)."""
 
@@ -143,6 +143,8 @@ class FusedAgents:
         self.actions = torch.full((self.batch, self.n_agents), -1, dtype=torch.int64, device=self.device)
         self.q = torch.zeros(self.batch, self.n_agents, self.n_actions, device=self.device)
         self.feat = torch.zeros(self.batch, 16, device=self.device) if self.conv else None
+        # sync_weights' verdict, written by the pack kernel: refused, tensor (PACK_WEIGHTS order), flat index, value bits
+        self.pack_status = torch.zeros(4, dtype=torch.int32, device=self.device)
         self.load_weights()
 
     def load_weights(self):
@@ -162,6 +164,42 @@ class FusedAgents:
             self.conv_w = [self.net.state_dict()[k].detach().to(self.device, torch.float32).contiguous().clone()
                            for k in ("conv.0.weight", "conv.0.bias", "conv.2.weight", "conv.2.bias", "linear.weight",
                                      "linear.bias")]
+
+    PACK_ORDER = ("fc1.weight", "fc1.bias", "rnn.weight_ih", "rnn.bias_ih", "rnn.weight_hh", "rnn.bias_hh", "fc2.0.weight",
+                  "fc2.0.bias", "fc2.2.weight", "fc2.2.bias")
+    PACK_WEIGHTS = ("fc1.weight", "rnn.weight_ih", "rnn.weight_hh", "fc2.0.weight", "fc2.2.weight")   # cs_policy_pack's check order
+    CONV_KEYS = ("conv.0.weight", "conv.0.bias", "conv.2.weight", "conv.2.bias", "linear.weight", "linear.bias")
+
+    def sync_weights(self):
+        """Repack `self.net`'s CURRENT parameters into `self.packed` in place, on the device: one launch of the pack kernel
+        (cs_policy_pack_device) on torch's current stream, plus device-to-device copies of the conv weights for flight.  Never
+        synchronises with the host, so a training loop can call it after every learn step.  A network that cs_policy_pack would
+        refuse (a weight-matrix entry not finite or beyond +-65504) leaves `self.packed` exactly as it was -- the previous
+        network keeps acting, as when load_weights() raises -- and check_weights() reports it."""
+        sd = self.net.state_dict()
+        ws = [sd[k].detach().to(self.device, torch.float32).contiguous() for k in self.PACK_ORDER]
+        if self._ops is not None:
+            self._ops.policy_pack_device(*ws, self.packed, self.pack_status)
+        else:
+            vp = lambda t: self._C.c_void_p(t.data_ptr())
+            with self._on_device():
+                self._check(self._L.cs_policy_pack_device(*[vp(w) for w in ws], ws[0].shape[1], self.n_actions, vp(self.packed),
+                                                          vp(self.pack_status), self._stream()))
+        if self.conv:
+            for dst, k in zip(self.conv_w, self.CONV_KEYS):
+                dst.copy_(sd[k].detach())
+
+    def check_weights(self):
+        """Raise CoopSearchError with cs_policy_pack's message if the last sync_weights() was refused (reads the pack kernel's
+        status: this synchronises)."""
+        import struct
+        refused, t, i, bits = (int(v) for v in self.pack_status.cpu())
+        if not refused:
+            return
+        v = struct.unpack("<f", struct.pack("<i", bits))[0]
+        txt = ("-nan" if bits < 0 else "nan") if v != v else "%g" % v   # printf's %g, as cs_policy_pack formats it (glibc signs NaN)
+        raise self._lib.CoopSearchError(f"cs_policy_pack: {self.PACK_WEIGHTS[t]}[{i}] = {txt} is outside the fp16 range (+-65504) "
+                                        "of the split-fp16 matrix path")
 
     def _stream(self):
         return self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)

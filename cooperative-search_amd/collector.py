@@ -184,7 +184,10 @@ class EpisodeCollector:
                     last = torch.nn.functional.one_hot(u[t], A).to(torch.float32)
                 env.refresh()
             if into is not None:
-                slots = torch.as_tensor(into._get_storage_idx(inc=B), device=dev)
+                # the ring positions (start + arange(B)) % size of _get_storage_idx, made on the device from the host cursor: a
+                # host-to-device copy of the index array would synchronise the stream
+                start = int(into._get_storage_idx(inc=B)[0])
+                slots = (torch.arange(B, dtype=torch.int64, device=dev) + start) % into.size
                 assemble_episodes(o, s, u, r, term, A, out=into.buffers, slots=slots)
                 episode = None
             else:
@@ -195,6 +198,10 @@ class EpisodeCollector:
             return episode, episode_reward, win_tag, targets_find
         finally:
             env.freeze_done, env.auto_reset = saved
+
+    def evaluate(self, policy, batches=1):
+        """`evaluate` (below) on this collector's env: Runner.evaluate's (win_rate, episode_reward, targets_find)."""
+        return evaluate(self.env, policy, batches)
 
 
 def _run_episodes(env, policy, init):

@@ -406,6 +406,99 @@ __global__ __launch_bounds__(PBLOCK, 4) void k_conv_features(ConvParams p) {
 #undef CONV_FETCH
 }
 
+// ---- cs_policy_pack on the device (cs_policy_pack_device): the learner's parameters -> the packed blob, no host round trip -----
+// ONE workgroup (inputs and blob are ~129 KB each).  Range pass: every weight entry in cs_policy_pack's check order (fc1.weight,
+// rnn.weight_ih, rnn.weight_hh, fc2.0.weight, fc2.2.weight; flat index within each) is tested with the host's predicate
+// !(|w| <= 65504); the smallest position in that order that fails is kept in LDS.  Barrier.  Then either the status names it and
+// the blob is NOT touched (all or nothing: the previous network keeps acting), or every dword of the blob is written: fragment
+// dwords through the same split_f16 as the host (two halves each, zero padding included) and the fp32 bias section as bit copies.
+constexpr int KBLOCK = 1024;
+
+struct PackParams {
+    const float *w[5];   // check order: fc1.weight [64][in_dim], rnn.weight_ih [192][64], rnn.weight_hh, fc2.0.weight [64][64], fc2.2.weight [A][64]
+    const float *b[5];   // fc1.bias [64], rnn.bias_ih [192], rnn.bias_hh [192], fc2.0.bias [64], fc2.2.bias [A]
+    int in_dim, n_actions;
+    float *packed;       // [PACKED_FLOATS]
+    int32_t *status;     // [4]: refused, tensor (check order), flat index, value bits  (0, -1, -1, 0 when packed)
+};
+
+__global__ __launch_bounds__(KBLOCK) void k_policy_pack(PackParams p) {
+    __shared__ int s_first;
+    const int tid = threadIdx.x;
+    const int n_w[5] = {64 * p.in_dim, 192 * 64, 192 * 64, 64 * 64, p.n_actions * 64};
+    if (tid == 0) s_first = 0x7fffffff;
+    __syncthreads();
+    // a thread's candidates come in increasing order: its first failure is its smallest, the LDS minimum the block's smallest
+    int base = 0, mine = 0x7fffffff;
+    for (int t = 0; t < 5 && mine == 0x7fffffff; t++) {
+        for (int i = tid; i < n_w[t]; i += KBLOCK)
+            if (!(fabsf(p.w[t][i]) <= F16_MAX)) {
+                mine = base + i;
+                break;
+            }
+        base += n_w[t];
+    }
+    if (mine != 0x7fffffff) atomicMin(&s_first, mine);
+    __syncthreads();
+    const int first = s_first;
+    if (first != 0x7fffffff) {
+        if (tid == 0) {
+            int t = 0, i = first;
+            while (i >= n_w[t]) i -= n_w[t++];
+            p.status[0] = 1;
+            p.status[1] = t;
+            p.status[2] = i;
+            p.status[3] = (int32_t)__float_as_uint(p.w[t][i]);
+        }
+        return;
+    }
+    if (tid == 0) {
+        p.status[0] = 0;
+        p.status[1] = -1;
+        p.status[2] = -1;
+        p.status[3] = 0;
+    }
+    uint32_t *out = reinterpret_cast<uint32_t *>(p.packed);
+    for (int d = tid; d < PACKED_FLOATS; d += KBLOCK) {
+        uint32_t word;
+        if (d < HOFF_B1) {
+            // fragment regions: (offset, weight, rows, columns, k-steps per column tile) as cs_policy_pack's hfrag calls
+            const float *w;
+            int off, n_out, k_in, nks;
+            if (d < HOFF_WIH) { off = HOFF_W1; w = p.w[0]; n_out = 64; k_in = p.in_dim; nks = 1; }
+            else if (d < HOFF_WHH) { off = HOFF_WIH; w = p.w[1]; n_out = 192; k_in = 64; nks = 2; }
+            else if (d < HOFF_W2) { off = HOFF_WHH; w = p.w[2]; n_out = 192; k_in = 64; nks = 2; }
+            else if (d < HOFF_W3) { off = HOFF_W2; w = p.w[3]; n_out = 64; k_in = 64; nks = 2; }
+            else { off = HOFF_W3; w = p.w[4]; n_out = p.n_actions; k_in = 64; nks = 2; }
+            const int f = (d - off) / FRAG_DW, q = (d - off) % FRAG_DW;
+            const int nt = f / nks, k0 = 32 * (f % nks);
+            const bool lo_plane = q >= FRAG_DW / 2;
+            const int l = (q % (FRAG_DW / 2)) >> 2, j0 = 2 * (q & 3);   // dword = halves j0, j0 + 1 of lane l
+            const int n = 16 * nt + (l & 15);
+            uint16_t hv[2];
+            for (int e = 0; e < 2; e++) {
+                const int k = k0 + 8 * (l >> 4) + j0 + e;
+                const float v = (n < n_out && k < k_in) ? w[(size_t)n * k_in + k] : 0.0f;
+                _Float16 hi, lo;
+                split_f16(v, hi, lo);
+                const _Float16 h = lo_plane ? lo : hi;
+                __builtin_memcpy(&hv[e], &h, 2);
+            }
+            word = (uint32_t)hv[0] | ((uint32_t)hv[1] << 16);
+        } else {
+            const float *b;
+            int i, n;
+            if (d < HOFF_BIH) { b = p.b[0]; i = d - HOFF_B1; n = 64; }
+            else if (d < HOFF_BHH) { b = p.b[1]; i = d - HOFF_BIH; n = 192; }
+            else if (d < HOFF_B2) { b = p.b[2]; i = d - HOFF_BHH; n = 192; }
+            else if (d < HOFF_B3) { b = p.b[3]; i = d - HOFF_B2; n = 64; }
+            else { b = p.b[4]; i = d - HOFF_B3; n = p.n_actions; }
+            word = i < n ? reinterpret_cast<const uint32_t *>(b)[i] : 0u;
+        }
+        out[d] = word;
+    }
+}
+
 thread_local char g_perr[200] = "";
 thread_local char g_lerr[200] = "";   // cs_gru_seq_*, cs_episode_returns
 
@@ -475,6 +568,27 @@ int cs_policy_pack(const float *fc1_w, const float *fc1_b, const float *w_ih, co
     for (int i = 0; i < 192; i++) packed[HOFF_BHH + i] = b_hh[i];
     for (int i = 0; i < 64; i++) packed[HOFF_B2 + i] = fc2a_b[i];
     for (int i = 0; i < n_actions; i++) packed[HOFF_B3 + i] = fc2b_b[i];
+    return CS_OK;
+}
+
+// cs_policy_pack on the device, one launch on `stream` (k_policy_pack): same blob word for word, same refusal -- reported in
+// status_dev[4] instead of a return code, the blob left as it was.  Only argument errors are returned (before any launch).
+int cs_policy_pack_device(const float *fc1_w, const float *fc1_b, const float *w_ih, const float *b_ih, const float *w_hh,
+                          const float *b_hh, const float *fc2a_w, const float *fc2a_b, const float *fc2b_w, const float *fc2b_b,
+                          int in_dim, int n_actions, float *packed_dev, int32_t *status_dev, void *stream) {
+    if (!fc1_w || !fc1_b || !w_ih || !b_ih || !w_hh || !b_hh || !fc2a_w || !fc2a_b || !fc2b_w || !fc2b_b || !packed_dev ||
+        !status_dev || in_dim < 1 || in_dim > KIN_MAX || n_actions < 1 || n_actions > 16) {
+        snprintf(g_perr, sizeof(g_perr), "cs_policy_pack_device: bad argument (in_dim %d must be 1..32, n_actions %d 1..16; "
+                 "no pointer may be null)", in_dim, n_actions);
+        return CS_E_ARG;
+    }
+    const PackParams p{{fc1_w, w_ih, w_hh, fc2a_w, fc2b_w}, {fc1_b, b_ih, b_hh, fc2a_b, fc2b_b}, in_dim, n_actions, packed_dev,
+                       status_dev};
+    hipLaunchKernelGGL(k_policy_pack, dim3(1), dim3(KBLOCK), 0, (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_perr, sizeof(g_perr), "cs_policy_pack_device: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
     return CS_OK;
 }
 

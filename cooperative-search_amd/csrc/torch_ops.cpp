@@ -262,6 +262,35 @@ void policy_conv_features(const Tensor &c1w, const Tensor &c1b, const Tensor &c2
     TORCH_CHECK(rc == CS_OK, cs_policy_last_error());
 }
 
+// FusedAgents.sync_weights: the agent network's ten torch-layout parameters -> the packed blob in place, one launch
+// (cs_policy_pack_device); a refused weight leaves `packed` as it was and is reported in `status` (int32 [4]), never here
+void policy_pack_device(const Tensor &fc1_w, const Tensor &fc1_b, const Tensor &w_ih, const Tensor &b_ih, const Tensor &w_hh,
+                        const Tensor &b_hh, const Tensor &fc2a_w, const Tensor &fc2a_b, const Tensor &fc2b_w, const Tensor &fc2b_b,
+                        Tensor packed, Tensor status) {
+    check_f32(packed, "packed", (int64_t)cs_policy_packed_floats(), packed);
+    check_dev(status, "status", at::kInt, 4, packed);
+    TORCH_CHECK(fc1_w.dim() == 2 && fc1_w.size(0) == 64 && fc1_w.size(1) >= 1 && fc1_w.size(1) <= 32,
+                "coopsearch: fc1.weight must be [64, in_dim] with in_dim 1..32");
+    TORCH_CHECK(fc2b_w.dim() == 2 && fc2b_w.size(1) == 64 && fc2b_w.size(0) >= 1 && fc2b_w.size(0) <= 16,
+                "coopsearch: fc2.2.weight must be [n_actions, 64] with n_actions 1..16");
+    const int64_t in_dim = fc1_w.size(1), A = fc2b_w.size(0);
+    check_f32(fc1_w, "fc1.weight", 64 * in_dim, packed);
+    check_f32(fc1_b, "fc1.bias", 64, packed);
+    check_f32(w_ih, "rnn.weight_ih", 192 * 64, packed);
+    check_f32(b_ih, "rnn.bias_ih", 192, packed);
+    check_f32(w_hh, "rnn.weight_hh", 192 * 64, packed);
+    check_f32(b_hh, "rnn.bias_hh", 192, packed);
+    check_f32(fc2a_w, "fc2.0.weight", 64 * 64, packed);
+    check_f32(fc2a_b, "fc2.0.bias", 64, packed);
+    check_f32(fc2b_w, "fc2.2.weight", A * 64, packed);
+    check_f32(fc2b_b, "fc2.2.bias", A, packed);
+    const int rc = cs_policy_pack_device(fc1_w.data_ptr<float>(), fc1_b.data_ptr<float>(), w_ih.data_ptr<float>(), b_ih.data_ptr<float>(),
+                                         w_hh.data_ptr<float>(), b_hh.data_ptr<float>(), fc2a_w.data_ptr<float>(), fc2a_b.data_ptr<float>(),
+                                         fc2b_w.data_ptr<float>(), fc2b_b.data_ptr<float>(), (int)in_dim, (int)A, packed.data_ptr<float>(),
+                                         status.data_ptr<int32_t>(), stream_of(packed));
+    TORCH_CHECK(rc == CS_OK, cs_policy_last_error());
+}
+
 // the exploration schedule of common/rollout.py:35-41,75-76,133-135 as a cs_epsilon: `eps_env` (float64 [B], in / out) carries
 // every env's own epsilon across calls; `eps_trace` (float64 [T, B], out) records what each step's selection used
 static cs_epsilon schedule_of(double epsilon, c10::optional<Tensor> &eps_env, double anneal, double min_epsilon, bool per_step,
@@ -459,6 +488,8 @@ TORCH_LIBRARY(coopsearch, m) {
           "Tensor(b!)? trace_row) -> ()", &epsilon_step);
     m.def("policy_conv_features(Tensor conv1_w, Tensor conv1_b, Tensor conv2_w, Tensor conv2_b, Tensor lin_w, Tensor lin_b, "
           "Tensor maps, int map_stride, int n_maps, Tensor(a!) feat) -> ()", &policy_conv_features);
+    m.def("policy_pack_device(Tensor fc1_w, Tensor fc1_b, Tensor w_ih, Tensor b_ih, Tensor w_hh, Tensor b_hh, Tensor fc2a_w, "
+          "Tensor fc2a_b, Tensor fc2b_w, Tensor fc2b_b, Tensor(a!) packed, Tensor(b!) status) -> ()", &policy_pack_device);
     m.def("rollout_policy(Tensor cfg, Tensor(a!) state, Tensor packed, Tensor(b!) hidden, Tensor last, int T, int flags, "
           "float epsilon, Tensor(j!)? eps_env, float anneal, float min_epsilon, bool per_step, Tensor(k!)? eps_trace, int seed, "
           "int step0, int row0, int select, Tensor(c!) actions, Tensor(d!) reward, Tensor(e!) terminated, "

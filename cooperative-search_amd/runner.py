@@ -1,0 +1,178 @@
+"""The training driver: the reference's `Runner.run` (runner.py:41-84, with agent/agent.py:112-136 for train / save) over the
+device-resident pieces -- `EpisodeCollector` (rows f1 / f4), `DeviceReplayBuffer` (f2), `FusedAgents` (f3) and the learners.
+
+One epoch is: evaluate (every `evaluate_cycle` epochs, epoch 0 included) -> collect `n_episodes` batches of B episodes with
+exploration -> off-policy: store them in the ring and make `train_steps` learn calls on samples of min(current_size,
+batch_size); on-policy: one learn call on the batches concatenated along the episode axis -> after EVERY learn call the acting
+network follows the learner through `FusedAgents.sync_weights()` (the pack kernel, on the device).  Checkpoints are written
+where the reference's Agents.train writes them (train_step > 0 and train_step % save_cycle == 0), numbered by its
+get_model_idx rule.  Between evaluation and save points an epoch never synchronises with the host: the ring slots are made on
+the device, the repack is one launch, and epsilon reaches the learner as a device scalar.
+
+Batched semantics: one epoch stores B * n_episodes episodes but makes `train_steps` learn calls, as the
+reference's makes them on its n_episodes; an evaluation covers ceil(evaluate_epoch / B) batches, i.e. at least evaluate_epoch
+episodes.  DOP and REINFORCE take the epsilon of env 0 (`schedule.values[0]`): the reference has one RolloutWorker and one
+epsilon, a batch of B envs carries B of them (collector.EpsilonSchedule), and env 0 anneals exactly as that one worker would.
+"""
+import math
+import os
+
+import numpy as np
+import torch
+
+from .agents import FusedAgents
+from .collector import EpisodeCollector, EpsilonSchedule
+from .learner import DOPLearner, QMixLearner, ReinforceLearner
+from .replay import KEYS, DeviceReplayBuffer
+
+# fields the reference's get_mixer_args / get_common_args set and this package's get_*_args leave to the caller
+# (common/arguments.py:43-46, :84-104)
+RUN_DEFAULTS = dict(n_epoch=500000, n_episodes=1, train_steps=1, evaluate_cycle=200, save_cycle=500, evaluate_epoch=20,
+                    model_dir="./model/", result_dir="./result/", load_model=False)
+LEARNERS = {"qmix": QMixLearner, "dop": DOPLearner, "reinforce": ReinforceLearner}
+# the checkpoint file whose presence get_model_idx() - 1 must show when resuming (the reference learners' __init__)
+_RESUME = {"qmix": ("rnn", "qmix"), "dop": ("actor", "critic", "mixer"), "reinforce": ("rnn",)}
+
+
+def run_name(args):
+    """<env>_Seed<seed>_<alg>_<n>a<targets>t(AM<agent_mode>TM<target_mode>): runner.py:31-38's directory name."""
+    return (args.env + "_Seed" + str(args.seed) + "_" + args.alg +
+            "_{}a{}t(AM{}TM{})".format(args.n_agents, args.target_num, args.agent_mode, args.target_mode))
+
+
+def get_model_idx(model_dir):
+    """The reference learners' get_model_idx (policy/qmix.py:197-207): 1 + the largest leading integer of the file names in
+    model_dir; 0 (creating the directory) when it is missing."""
+    if not os.path.exists(model_dir):
+        os.makedirs(model_dir)
+        return 0
+    idx = 0
+    for name in os.listdir(model_dir):
+        idx = max(idx, int(name.split("_")[0]))
+    return idx + 1
+
+
+def apply_run_defaults(args):
+    """RUN_DEFAULTS for the fields `args` does not carry (existing values are kept)."""
+    for k, v in RUN_DEFAULTS.items():
+        if not hasattr(args, k):
+            setattr(args, k, v)
+    return args
+
+
+class Runner:
+    """Runner(env, args): `env` a BatchedFlightEnv; `args` the reference's namespace after get_mixer_args / get_dop_args /
+    get_reinforce_args and apply_env_info; args.alg selects the learner.  The parts (learner, agents, schedule, collector,
+    buffer) are built here unless passed in."""
+
+    def __init__(self, env, args, learner=None, agents=None, schedule=None, collector=None, buffer=None):
+        alg = getattr(args, "alg", None)
+        if alg in ("vdn", "random"):
+            raise ValueError(f"Runner: alg {alg!r} is not trained here (VDN and random have no device learner)")
+        if alg not in LEARNERS:
+            raise ValueError(f"Runner: no such algorithm {alg!r} (qmix, dop or reinforce)")
+        self.env, self.args = env, apply_run_defaults(args)
+        device = getattr(env, "device", "cuda")
+        self.learner = learner if learner is not None else LEARNERS[alg](args, device)
+        self.model_path = args.model_dir + run_name(args)
+        if args.load_model:   # policy/*.py __init__: the newest checkpoint of the learner's own directory
+            idx = get_model_idx(self.model_path) - 1
+            files = [os.path.join(self.model_path, f"{idx}_{part}_net_params.pkl") for part in _RESUME[alg]]
+            if not os.path.exists(files[0]):
+                raise Exception("No model!")
+            self.learner.load_model(*files)
+        if agents is None:   # the learner's acting network itself (agent.py:58-61): its parameters ARE the learner's
+            acting = self.learner.actor if alg == "dop" else self.learner.eval_rnn
+            agents = FusedAgents(args, env.batch, device, net=acting, seed=args.seed)
+        self.agents = agents
+        self.schedule = schedule if schedule is not None else EpsilonSchedule(args, env.batch, device)
+        self.collector = collector if collector is not None else EpisodeCollector(env, self.schedule)
+        self.buffer = None
+        if args.off_policy:
+            self.buffer = buffer if buffer is not None else DeviceReplayBuffer(args, args.buffer_size, device)
+        self.win_rates, self.targets_find, self.episode_rewards = [], [], []
+        self.result_path = args.result_dir + run_name(args)
+        os.makedirs(self.result_path, exist_ok=True)   # runner.py:33-39
+        os.makedirs(self.model_path, exist_ok=True)
+
+    def run(self, num, n_epoch=None):
+        """runner.py:41-84 for n_epoch epochs (default args.n_epoch); results are saved after every evaluation and at the end."""
+        a = self.args
+        n_epoch = a.n_epoch if n_epoch is None else int(n_epoch)
+        train_steps = 0
+        for epoch in range(n_epoch):
+            if epoch % a.evaluate_cycle == 0:
+                win_rate, episode_reward, targets_find = self.evaluate()
+                self.win_rates.append(win_rate)
+                self.targets_find.append(targets_find)
+                self.episode_rewards.append(episode_reward)
+                self.save_results(num)
+            train_steps = self.train_epoch(train_steps)
+        self.save_results(num)
+
+    def train_epoch(self, train_steps):
+        """Collect, store, learn, repack: one epoch without its evaluation.  Returns the updated learn-call count."""
+        a = self.args
+        if a.off_policy:
+            for idx in range(a.n_episodes):
+                self.collector.generate_episodes(agents=self.agents, evaluate=False, episode_num=idx, into=self.buffer)
+            for _ in range(a.train_steps):
+                self.train(self.buffer.sample(min(self.buffer.current_size, a.batch_size)), train_steps)
+                train_steps += 1
+        else:
+            eps = [self.collector.generate_episodes(agents=self.agents, evaluate=False, episode_num=idx)[0]
+                   for idx in range(a.n_episodes)]
+            batch = eps[0] if len(eps) == 1 else {k: torch.cat([e[k] for e in eps], 0) for k in KEYS}
+            self.train(batch, train_steps)
+            train_steps += 1
+        return train_steps
+
+    def train(self, batch, train_step):
+        """agent.py:112-136: one learn call (QMIX without epsilon, DOP and REINFORCE with env 0's), the acting network repacked,
+        a checkpoint when train_step > 0 and train_step % save_cycle == 0."""
+        if self.args.alg == "qmix":
+            self.learner.learn(batch, None, train_step)
+        else:
+            self.learner.learn(batch, None, train_step, self.schedule.values[0])
+        self.agents.sync_weights()
+        if train_step > 0 and train_step % self.args.save_cycle == 0:
+            self.agents.check_weights()   # the host waits here anyway
+            self.learner.save_model(get_model_idx(self.model_path))
+
+    def evaluate(self):
+        """runner.py:86-96 -> (win_rate, episode_reward, targets_find): the greedy policy over ceil(evaluate_epoch / B) batches."""
+        self.agents.check_weights()
+        batches = max(1, math.ceil(self.args.evaluate_epoch / self.env.batch))
+        return self.collector.evaluate(self.agents.policy(0.0, True), batches)
+
+    def save_results(self, num):
+        """runner.py:98-116: targets_find_<num>.npy (search envs) and episode_rewards_<num>.npy; plt_<num>.png when matplotlib
+        is available."""
+        a = self.args
+        self._plot(num)
+        if getattr(a, "search_env", True):
+            np.save(os.path.join(self.result_path, "targets_find_{}".format(num)), self.targets_find)
+        np.save(os.path.join(self.result_path, "episode_rewards_{}".format(num)), self.episode_rewards)
+
+    def _plot(self, num):
+        try:
+            import matplotlib
+            matplotlib.use("Agg", force=False)
+            import matplotlib.pyplot as plt
+        except Exception:   # noqa: BLE001  (no matplotlib, or no usable backend: the picture is optional)
+            return
+        a = self.args
+        plt.figure()
+        plt.axis([0, a.n_epoch, 0, 100])
+        plt.cla()
+        if getattr(a, "search_env", True):
+            plt.subplot(2, 1, 1)
+            plt.plot(range(len(self.targets_find)), self.targets_find)
+            plt.xlabel("epoch*{}".format(a.evaluate_cycle))
+            plt.ylabel("targets_find")
+            plt.subplot(2, 1, 2)
+        plt.plot(range(len(self.episode_rewards)), self.episode_rewards)
+        plt.xlabel("epoch*{}".format(a.evaluate_cycle))
+        plt.ylabel("episode_rewards")
+        plt.savefig(os.path.join(self.result_path, "plt_{}.png".format(num)), format="png")
+        plt.close()

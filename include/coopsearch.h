@@ -37,8 +37,8 @@ extern "C" {
                               4: cs_source_hash, CS_KERNEL_OCT; 5: CS_KERNEL_ODE; 6: cs_epsilon (exploration schedule),
                               cs_epsilon_step, CS_KERNEL_LANEV; 7: CS_CHECK_ACTIONS, cs_has_legacy_kernels;
                               still 7: cs_gru_seq_forward, cs_gru_seq_backward, cs_learn_last_error were ADDED, then
-                              cs_episode_returns (no existing export or struct changed: a version-7 caller works
-                              unchanged) */
+                              cs_episode_returns, then cs_policy_pack_device (no existing export or struct changed: a
+                              version-7 caller works unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
 #define CS_MAX_MAP 64
@@ -264,6 +264,19 @@ size_t cs_policy_packed_floats(void);
 int cs_policy_pack(const float *fc1_w, const float *fc1_b, const float *w_ih, const float *b_ih, const float *w_hh,
                    const float *b_hh, const float *fc2a_w, const float *fc2a_b, const float *fc2b_w, const float *fc2b_b,
                    int in_dim, int n_actions, float *packed_host);
+
+/* DEVICE: cs_policy_pack in ONE launch on `stream`, every pointer a device pointer (the learner's parameters where they live;
+ * packed_dev [cs_policy_packed_floats()]).  For every weight that cs_policy_pack accepts, the blob is cs_policy_pack's output word
+ * for word (the same split_f16 conversions, zero padding and fp32 biases; every word is written).  cs_policy_pack's refusal is
+ * kept, all or nothing, without a host synchronisation: if any entry of the five weight matrices is not finite or exceeds 65504
+ * in magnitude, packed_dev is left exactly as it was and status_dev (int32 [4]) receives {1, tensor, index, value bits} -- tensor
+ * in cs_policy_pack's check order (0 fc1.weight, 1 rnn.weight_ih, 2 rnn.weight_hh, 3 fc2.0.weight, 4 fc2.2.weight), the FIRST
+ * offending flat index in that order and the float's bits; otherwise status_dev = {0, -1, -1, 0}.  Returns CS_E_ARG (null
+ * pointer, in_dim outside 1..32, n_actions outside 1..16) before any launch, CS_E_LAUNCH if the launch fails. */
+int cs_policy_pack_device(const float *fc1_w, const float *fc1_b, const float *w_ih, const float *b_ih, const float *w_hh,
+                          const float *b_hh, const float *fc2a_w, const float *fc2a_b, const float *fc2b_w,
+                          const float *fc2b_b, int in_dim, int n_actions, float *packed_dev, int32_t *status_dev,
+                          void *stream);
 
 /* One forward over rows = B*n (row r: env r / n_agents, agent r % n_agents).  obs row r = 4 floats at
  * obs_dev + r*obs_stride + obs_offset (floats); last_dev[r] = previous action or < 0 for none
