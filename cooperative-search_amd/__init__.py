@@ -10,7 +10,7 @@ from .args import get_flight_easy_args, get_flight_args, make_env_args, apply_en
 from .env import BatchedFlightEnv, FlightSearchEnvEasy, FlightSearchEnv  # noqa: F401
 from . import _lib as lib  # noqa: F401
 from . import dist  # noqa: F401
-from .replay import DeviceReplayBuffer  # noqa: F401
+from .replay import COMPACT_KEYS, CompactReplayBuffer, DeviceReplayBuffer, compact_from_dense, expand_compact  # noqa: F401
 from .agents import AgentRNN, BatchedAgents, FusedAgents, rnn_input_shape  # noqa: F401
 from .collector import EpisodeCollector, EpsilonSchedule, evaluate, collect_experiment_data, random_policy  # noqa: F401
 from .learner import GRUSequence, MixerNet, QMixLearner, get_mixer_args, unroll_q  # noqa: F401

@@ -17,8 +17,8 @@ SELECT_SOFTMAX, SELECT_SAMPLE = 1, 2
 FREEZE_DONE, AUTO_RESET, ACTIONS_I64, KERNEL_GROUP, KERNEL_LANE, KERNEL_SOLO, KERNEL_DUO, KERNEL_OCT, KERNEL_OD, KERNEL_ODE, KERNEL_LANEV, CHECK_ACTIONS = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048
 
 EXPORTS = ["cs_abi_version", "cs_source_hash", "cs_has_legacy_kernels", "cs_last_error", "cs_state_layout", "cs_init", "cs_seed", "cs_reset", "cs_step",
-           "cs_rollout", "cs_rollout_policy", "cs_rollout_policy_flight", "cs_emit", "cs_metrics", "cs_mt_canonical", "cs_mt_advance", "cs_policy_packed_floats", "cs_policy_pack", "cs_policy_pack_device", "cs_policy_forward",
-           "cs_policy_conv_features", "cs_policy_last_error", "cs_store_episodes", "cs_episodes_last_error", "cs_epsilon_step",
+           "cs_rollout", "cs_rollout_policy", "cs_rollout_policy_flight", "cs_collect_flight", "cs_emit", "cs_metrics", "cs_mt_canonical", "cs_mt_advance", "cs_policy_packed_floats", "cs_policy_pack", "cs_policy_pack_device", "cs_policy_forward",
+           "cs_policy_conv_features", "cs_policy_last_error", "cs_store_episodes", "cs_store_episodes_compact", "cs_episodes_last_error", "cs_epsilon_step",
            "cs_gru_seq_forward", "cs_gru_seq_backward", "cs_episode_returns", "cs_learn_last_error"]
 
 
@@ -44,6 +44,11 @@ class CsLayout(C.Structure):
 class CsEpisodeOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("o", "u", "s", "r", "o_next", "s_next", "avail_u", "avail_u_next", "u_onehot",
                                           "padded", "terminated")]
+
+
+class CsCompactOut(C.Structure):
+    """cs_compact_out of include/coopsearch.h: the destinations of the map-once episode keys (replay.COMPACT_KEYS order)."""
+    _fields_ = [(k, C.c_void_p) for k in ("map", "s_full", "u", "r", "padded", "terminated")]
 
 
 class CsEpsilon(C.Structure):
@@ -97,6 +102,7 @@ def load():
                                     C.c_uint64, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.cs_rollout_policy_flight.argtypes = [C.POINTER(CsConfig)] + [vp] * 11 + [C.c_int, C.c_int, C.POINTER(CsEpsilon), C.c_uint64, C.c_uint32,
                                            C.c_uint64, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.cs_collect_flight.argtypes = L.cs_rollout_policy_flight.argtypes   # map / state tables in place of obs / state_out
     L.cs_epsilon_step.argtypes = [C.POINTER(CsConfig), vp, C.c_int, vp, C.c_double, C.c_double, vp, vp]
     L.cs_emit.argtypes = [C.POINTER(CsConfig), vp, vp, vp, vp]
     L.cs_metrics.argtypes = [C.POINTER(CsConfig), vp, vp, vp]
@@ -106,6 +112,7 @@ def load():
     L.cs_policy_last_error.restype = C.c_char_p
     L.cs_episodes_last_error.restype = C.c_char_p
     L.cs_store_episodes.argtypes = [C.c_int] * 6 + [vp] * 6 + [C.POINTER(CsEpisodeOut), vp]
+    L.cs_store_episodes_compact.argtypes = [C.c_int] * 5 + [vp] * 6 + [C.POINTER(CsCompactOut), vp]
     L.cs_policy_pack.argtypes = [vp] * 10 + [C.c_int, C.c_int, vp]
     L.cs_policy_pack_device.argtypes = [vp] * 10 + [C.c_int, C.c_int, vp, vp, vp]
     L.cs_policy_forward.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int,

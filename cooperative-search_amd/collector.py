@@ -18,7 +18,7 @@ import torch
 
 from . import _lib
 from . import dist as _dist
-from .replay import KEYS
+from .replay import COMPACT_KEYS, KEYS
 
 
 def assemble_episodes(o, s, u, r, term, n_actions, out=None, slots=None):
@@ -49,6 +49,40 @@ def assemble_episodes(o, s, u, r, term, n_actions, out=None, slots=None):
         rc = L.cs_store_episodes(B, T, n, A, w, S, o.data_ptr(), s.data_ptr(), u.data_ptr(), r.data_ptr(),
                                  term.view(torch.uint8).data_ptr(), slots.data_ptr() if slots is not None else None,
                                  C.byref(eo), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise _lib.CoopSearchError(L.cs_episodes_last_error().decode())
+    return out
+
+
+def assemble_episodes_compact(m, s, u, r, term, out=None, slots=None):
+    """Step-major tables -> the map-once episode keys (replay.COMPACT_KEYS) with one kernel pass over the wide keys
+    (cs_store_episodes_compact).  m [T+1, B, cells], s [T+1, B, S], u int64 [T, B, n], r [T, B], term bool/uint8 [T, B]
+    (device, contiguous); out / slots as in assemble_episodes (destinations [slots, T + 1, ...] for map and s_full).
+    Equals replay.compact_from_dense(assemble_episodes_torch(...)) of the dense tables, without ever holding them."""
+    T, B, n = u.shape
+    cells, S = m.shape[-1], s.shape[-1]
+    dev = m.device
+    if out is None:
+        shapes = {"map": (B, T + 1, cells), "s_full": (B, T + 1, S), "u": (B, T, n, 1), "r": (B, T, 1), "padded": (B, T, 1),
+                  "terminated": (B, T, 1)}
+        out = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in COMPACT_KEYS}
+    for t in (m, s, u, r, term) + tuple(out[k] for k in COMPACT_KEYS):
+        if not t.is_contiguous() or t.device != dev:
+            raise ValueError("assemble_episodes_compact: tensors must be contiguous and on one device")
+    if any(out[k].dtype != torch.float32 for k in COMPACT_KEYS) or u.dtype != torch.int64:
+        raise ValueError("assemble_episodes_compact: destinations must be float32 and u int64")
+    ops = _lib.pick_binding(None)[1]
+    if ops is not None:   # torch.ops.coopsearch.store_episodes_compact: checks in C++, torch's stream
+        ops.store_episodes_compact(m, s, u, r, term.view(torch.uint8), slots, [out[k] for k in COMPACT_KEYS])
+        return out
+    L = _lib.load()
+    if any(out[k].shape[1] != (T + 1 if k in ("map", "s_full") else T) for k in COMPACT_KEYS):
+        raise ValueError("assemble_episodes_compact: destinations must be [slots, T (+ 1), ...]")
+    co = _lib.CsCompactOut(**{k: out[k].data_ptr() for k in COMPACT_KEYS})
+    with torch.cuda.device(dev):   # the launch goes to the process's current device
+        rc = L.cs_store_episodes_compact(B, T, n, cells, S, m.data_ptr(), s.data_ptr(), u.data_ptr(), r.data_ptr(),
+                                         term.view(torch.uint8).data_ptr(), slots.data_ptr() if slots is not None else None,
+                                         C.byref(co), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     if rc != 0:
         raise _lib.CoopSearchError(L.cs_episodes_last_error().decode())
     return out
@@ -119,7 +153,7 @@ class EpisodeCollector:
         self.schedule = schedule
 
     def generate_episodes(self, policy=None, actions=None, init=False, agents=None, epsilon=0.0, evaluate=True,
-                          one_launch=True, into=None, episode_num=None, eps_trace=None):
+                          one_launch=True, into=None, episode_num=None, eps_trace=None, compact=False):
         """One episode per env.  Either `actions` (open-loop table, int [T, B, n]; flight_easy runs it as ONE fused
         rollout launch), `policy(obs[B,n,obs], state[B,S], last_onehot[B,n,A], t) -> int actions [B, n]`, or `agents`
         (a `FusedAgents`: flight_easy with n <= 5 and one_launch: the WHOLE episode -- T x (network forward, env step)
@@ -130,8 +164,17 @@ class EpisodeCollector:
         With a schedule (see __init__) and evaluate=False the envs explore with their own, annealing epsilon
         (episode_num: the reference's argument, only the 'epoch' scale looks at it; eps_trace: float64 [T, B] that receives the
         epsilon of every step's selection).
+        compact=True (flight with `agents`, a `FusedAgents`): the episodes are collected and returned in the map-once format
+        (replay.COMPACT_KEYS; `into` a `CompactReplayBuffer`) by one `env.collect_flight` call and one
+        `cs_store_episodes_compact` pass: every probability map is written once per step, no observation table exists.
+        `replay.expand_compact` of the result equals what compact=False returns from the same seeds.
         Returns (episode dict of float32 [B, T, ...] tensors, episode_reward[B], win_tag[B] bool, targets_find[B])."""
         env = self.env
+        if compact and (not env.flight or agents is None or not getattr(agents, "conv", False)):
+            raise ValueError("generate_episodes(compact=True) needs the flight variant and `agents`, a FusedAgents")
+        if into is not None and tuple(getattr(into, "keys", KEYS)) != (COMPACT_KEYS if compact else KEYS):
+            raise ValueError("generate_episodes(into=...): compact=True stores into a CompactReplayBuffer, compact=False "
+                             "into a DeviceReplayBuffer")
         sched = self.schedule if (self.schedule is not None and not evaluate and agents is not None) else None
         if sched is not None:
             sched.begin_episode(episode_num)
@@ -143,6 +186,8 @@ class EpisodeCollector:
         env.freeze_done, env.auto_reset = True, False  # finished envs must stay put; their steps become padding
         try:
             env.reset(init=init)  # rollout.py:26
+            if compact:
+                return self._collect_compact(agents, epsilon, evaluate, into, kw)
             obs_w, S = env.obs_width, env.state_shape
             o = torch.empty(T + 1, B, n, obs_w, dtype=torch.float32, device=dev)
             s = torch.empty(T + 1, B, S, dtype=torch.float32, device=dev)
@@ -198,6 +243,27 @@ class EpisodeCollector:
             return episode, episode_reward, win_tag, targets_find
         finally:
             env.freeze_done, env.auto_reset = saved
+
+    def _collect_compact(self, agents, epsilon, evaluate, into, kw):
+        """generate_episodes(compact=True) after the reset: the closed loop fills one map table and one state table
+        ([T+1, B, ...], n-independent), the assembly pass turns them into the compact keys."""
+        env = self.env
+        B, n, T, dev = env.batch, env.n_agents, env.time_limit, env.device
+        m = torch.empty(T + 1, B, env.cells, dtype=torch.float32, device=dev)
+        s = torch.empty(T + 1, B, env.state_shape, dtype=torch.float32, device=dev)
+        u = torch.empty(T, B, n, dtype=torch.int64, device=dev)
+        r = torch.empty(T, B, dtype=torch.float32, device=dev)
+        term = torch.empty(T, B, dtype=torch.bool, device=dev)
+        agents.init_hidden()
+        env.collect_flight(agents, T, epsilon, evaluate, out=dict(actions=u, reward=r, terminated=term, map=m, state=s), **kw)
+        if into is not None:
+            start = int(into._get_storage_idx(inc=B)[0])   # ring slots made on the device, as in the dense route
+            slots = (torch.arange(B, dtype=torch.int64, device=dev) + start) % into.size
+            assemble_episodes_compact(m, s, u, r, term, out=into.buffers, slots=slots)
+            episode = None
+        else:
+            episode = assemble_episodes_compact(m, s, u, r, term)
+        return episode, env.total_reward.to(torch.float32).clone(), env.win_flag.clone(), env.target_find.clone()
 
     def evaluate(self, policy, batches=1):
         """`evaluate` (below) on this collector's env: Runner.evaluate's (win_rate, episode_reward, targets_find)."""

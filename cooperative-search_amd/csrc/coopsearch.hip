@@ -2249,20 +2249,30 @@ int cs_rollout_policy(const cs_config *cfg, void *state_dev, const float *packed
     return launched("cs_rollout_policy");
 }
 
-int cs_rollout_policy_flight(const cs_config *cfg, void *state_dev, const float *packed_dev, const float *conv1_w_dev,
-                             const float *conv1_b_dev, const float *conv2_w_dev, const float *conv2_b_dev,
-                             const float *lin_w_dev, const float *lin_b_dev, float *hidden_dev, const int64_t *last_dev,
-                             float *scratch_dev, int T, int flags, const cs_epsilon *eps, uint64_t seed, uint32_t step0, uint64_t row0,
-                             int select, int64_t *actions_dev, float *reward_dev, uint8_t *terminated_dev, uint8_t *win_dev,
-                             float *obs_dev, float *state_out_dev, void *stream) {
+// The flight closed loop behind cs_rollout_policy_flight and cs_collect_flight: T x (conv features of the map where it lives ->
+// network forward -> schedule step -> env step -> map sweep).  What the sweep writes beside the update is the caller's choice:
+// obs_dev: the n observation copies (k_map); map_tab: ONE snapshot per env and step (k_map_snap), with row 0 = the map on entry
+// and state_tab row 0 = get_state() on entry; neither: nothing (k_map_update).
+static int flight_closed_loop(const char *what, const cs_config *cfg, void *state_dev, const float *packed_dev,
+                              const float *conv1_w_dev, const float *conv1_b_dev, const float *conv2_w_dev, const float *conv2_b_dev,
+                              const float *lin_w_dev, const float *lin_b_dev, float *hidden_dev, const int64_t *last_dev,
+                              float *scratch_dev, int T, int flags, const cs_epsilon *eps, uint64_t seed, uint32_t step0,
+                              uint64_t row0, int select, int64_t *actions_dev, float *reward_dev, uint8_t *terminated_dev,
+                              uint8_t *win_dev, float *obs_dev, float *state_out_dev, float *map_tab, float *state_tab,
+                              void *stream) {
     DevParams p;
     int rc = make_params(cfg, state_dev, &p);
     if (rc) return rc;
     const cs_epsilon greedy = {0.0, 0.0, 0.0, 0, 0, nullptr, nullptr};
     if (!eps) eps = &greedy;
+    char msg[96];
+    auto bad = [&](int code, const char *why) {
+        snprintf(msg, sizeof(msg), "%s: %s", what, why);
+        return fail(code, msg);
+    };
     if (eps->trace_dev && !eps->eps_dev) return fail(CS_E_ARG, "cs_epsilon: trace_dev needs eps_dev");
-    if (cfg->variant != 1) return fail(CS_E_CONFIG, "cs_rollout_policy_flight: flight only");
-    if (cfg->map_size != 50) return fail(CS_E_CONFIG, "cs_rollout_policy_flight: the conv front end is built for map_size 50");
+    if (cfg->variant != 1) return bad(CS_E_CONFIG, "flight only");
+    if (cfg->map_size != 50) return bad(CS_E_CONFIG, "the conv front end is built for map_size 50");
     if (T < 1) return fail(CS_E_ARG, "T must be >= 1");
     if (!packed_dev || !conv1_w_dev || !conv1_b_dev || !conv2_w_dev || !conv2_b_dev || !lin_w_dev || !lin_b_dev ||
         !hidden_dev || !last_dev || !scratch_dev || !actions_dev || !reward_dev || !terminated_dev || !win_dev)
@@ -2277,7 +2287,10 @@ int cs_rollout_policy_flight(const cs_config *cfg, void *state_dev, const float 
     DevParams pc = p;
     pc.obs_row_w = 4;
     pc.obs_feat_off = 0;
-    CS_DISPATCH_N(cfg->n_agents, hipLaunchKernelGGL(k_emit<N>, dim3(env_blocks(p)), dim3(BLOCK), 0, s, pc, tails, nullptr));
+    CS_DISPATCH_N(cfg->n_agents, hipLaunchKernelGGL(k_emit<N>, dim3(env_blocks(p)), dim3(BLOCK), 0, s, pc, tails, state_tab));
+    if (map_tab) {   // row 0: the map on entry (apply = 0: a pure copy sweep)
+        CS_DISPATCH_N(cfg->n_agents, hipLaunchKernelGGL(k_map_snap<N>, dim3((unsigned)p.B), dim3(MAP_UPD_BLOCK), 0, s, p, map_tab, 0, 0));
+    }
     for (int t = 0; t < T; t++) {
         // the conv front end reads each env's map where it lives: one read per env, no observation copy needed
         if (cs_policy_conv_features(conv1_w_dev, conv1_b_dev, conv2_w_dev, conv2_b_dev, lin_w_dev, lin_b_dev, p.prob,
@@ -2302,11 +2315,42 @@ int cs_rollout_policy_flight(const cs_config *cfg, void *state_dev, const float 
         if (obs_dev) {
             CS_DISPATCH_N(cfg->n_agents, hipLaunchKernelGGL(k_map<N>, map_grid(p), dim3(MAP_BLOCK), 0, s, p,
                                                             obs_dev + (size_t)t * B * obs_w, 1, 0));
+        } else if (map_tab) {   // the update and the step's one snapshot, row t + 1 of the table
+            CS_DISPATCH_N(cfg->n_agents, hipLaunchKernelGGL(k_map_snap<N>, dim3((unsigned)p.B), dim3(MAP_UPD_BLOCK), 0, s, p,
+                                                            map_tab + (size_t)(t + 1) * B * p.cells, 1, 0));
         } else {   // the update alone: fusing it into the conv kernel was measured slower
             CS_DISPATCH_N(cfg->n_agents, hipLaunchKernelGGL(k_map_update<N>, dim3((unsigned)p.B), dim3(MAP_UPD_BLOCK), 0, s, p, 0));
         }
     }
-    return launched("cs_rollout_policy_flight");
+    return launched(what);
+}
+
+int cs_rollout_policy_flight(const cs_config *cfg, void *state_dev, const float *packed_dev, const float *conv1_w_dev,
+                             const float *conv1_b_dev, const float *conv2_w_dev, const float *conv2_b_dev,
+                             const float *lin_w_dev, const float *lin_b_dev, float *hidden_dev, const int64_t *last_dev,
+                             float *scratch_dev, int T, int flags, const cs_epsilon *eps, uint64_t seed, uint32_t step0, uint64_t row0,
+                             int select, int64_t *actions_dev, float *reward_dev, uint8_t *terminated_dev, uint8_t *win_dev,
+                             float *obs_dev, float *state_out_dev, void *stream) {
+    return flight_closed_loop("cs_rollout_policy_flight", cfg, state_dev, packed_dev, conv1_w_dev, conv1_b_dev, conv2_w_dev,
+                              conv2_b_dev, lin_w_dev, lin_b_dev, hidden_dev, last_dev, scratch_dev, T, flags, eps, seed, step0, row0,
+                              select, actions_dev, reward_dev, terminated_dev, win_dev, obs_dev, state_out_dev, nullptr, nullptr,
+                              stream);
+}
+
+int cs_collect_flight(const cs_config *cfg, void *state_dev, const float *packed_dev, const float *conv1_w_dev,
+                      const float *conv1_b_dev, const float *conv2_w_dev, const float *conv2_b_dev, const float *lin_w_dev,
+                      const float *lin_b_dev, float *hidden_dev, const int64_t *last_dev, float *scratch_dev, int T, int flags,
+                      const cs_epsilon *eps, uint64_t seed, uint32_t step0, uint64_t row0, int select, int64_t *actions_dev,
+                      float *reward_dev, uint8_t *terminated_dev, uint8_t *win_dev, float *map_tab_dev, float *state_tab_dev,
+                      void *stream) {
+    if (!map_tab_dev || !state_tab_dev) return fail(CS_E_ARG, "cs_collect_flight: null map / state table");
+    if ((reinterpret_cast<size_t>(map_tab_dev) & 15) != 0) return fail(CS_E_ARG, "cs_collect_flight: map_tab_dev must be 16-byte aligned");
+    if (!cfg) return fail(CS_E_ARG, "null config");
+    const size_t W = 4 * (size_t)cfg->n_agents + 3 * (size_t)cfg->n_targets;   // rows 1.. of the state table are the steps' outputs
+    return flight_closed_loop("cs_collect_flight", cfg, state_dev, packed_dev, conv1_w_dev, conv1_b_dev, conv2_w_dev, conv2_b_dev,
+                              lin_w_dev, lin_b_dev, hidden_dev, last_dev, scratch_dev, T, flags, eps, seed, step0, row0, select,
+                              actions_dev, reward_dev, terminated_dev, win_dev, nullptr, state_tab_dev + (size_t)cfg->batch * W,
+                              map_tab_dev, state_tab_dev, stream);
 }
 
 int cs_epsilon_step(const cs_config *cfg, void *state_dev, int flags, double *eps_dev, double anneal, double min_epsilon,

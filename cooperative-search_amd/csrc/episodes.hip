@@ -93,6 +93,64 @@ __global__ __launch_bounds__(256) void k_episode_small(EpisodeParams p) {
     }
 }
 
+// ---- the map-once format (cs_store_episodes_compact) -------------------------------------------------
+struct CompactParams {
+    int B, T, n, cells, state_w;
+    const float *map_tab, *s_tab, *r_tab;
+    const int64_t *u_tab;
+    const uint8_t *term_tab;
+    const int64_t *slot;   // destination episode slot of env b (null: b)
+    cs_compact_out out;
+};
+
+// row t of map / s_full holds data while t <= L (L = the episode's real steps): row 0 always, row t >= 1 iff step t - 1 was
+// real (it is that step's o_next / s_next), i.e. iff the env had not terminated before step t - 1
+__device__ __forceinline__ bool row_is_live(const CompactParams &p, int t, int b) {
+    return t <= 1 || p.term_tab[(size_t)(t - 2) * p.B + b] == 0;
+}
+
+// rows: out[slot][t][:] = live ? tab[t][b][:] : 0 for t = 0..T, map and s_full in one pass.  grid (B, row chunks); every
+// thread moves VEC floats of a map row at a time (a row is read once and written once: 2 x 10 KB, against the dense
+// format's 2n reads and 2n writes of the same bytes).
+template <int VEC>
+__global__ __launch_bounds__(256) void k_compact_rows(CompactParams p, int t_per_block) {
+    const int b = blockIdx.x;
+    const size_t slot = p.slot ? (size_t)p.slot[b] : (size_t)b;
+    const int rows = p.T + 1;
+    const int t0 = blockIdx.y * t_per_block, t1 = min(rows, t0 + t_per_block);
+    const int mw = p.cells, sw = p.state_w;
+    using V = typename std::conditional<VEC == 4, float4, float>::type;
+    const int nt = t1 - t0;
+    const V zero = {};
+    for (int i = threadIdx.x; i < nt * (mw / VEC); i += blockDim.x) {
+        const int t = t0 + i / (mw / VEC), c = i % (mw / VEC);
+        V v = zero;   // (a select between a loaded value and a constant, not between two addresses)
+        if (row_is_live(p, t, b)) v = reinterpret_cast<const V *>(p.map_tab + ((size_t)t * p.B + b) * mw)[c];
+        reinterpret_cast<V *>(p.out.map + (slot * rows + t) * mw)[c] = v;
+    }
+    // state rows: wavefront = row, lane = column (no per-element division)
+    for (int tt = threadIdx.x >> 6; tt < nt; tt += 4) {
+        const int t = t0 + tt;
+        const bool live = row_is_live(p, t, b);
+        const float *src = p.s_tab + ((size_t)t * p.B + b) * sw;
+        float *dst = p.out.s_full + (slot * rows + t) * sw;
+        for (int c = threadIdx.x & 63; c < sw; c += 64) dst[c] = live ? src[c] : 0.0f;
+    }
+}
+
+// the narrow keys, one thread per (b, t): u, r, padded, terminated -- k_episode_small's values of the same names
+__global__ __launch_bounds__(256) void k_compact_small(CompactParams p) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)p.B * p.T) return;
+    const int b = (int)(i / p.T), t = (int)(i % p.T);
+    const size_t slot = p.slot ? (size_t)p.slot[b] : (size_t)b, e = slot * p.T + t;
+    const bool real = t == 0 || p.term_tab[(size_t)(t - 1) * p.B + b] == 0;
+    p.out.r[e] = real ? p.r_tab[(size_t)t * p.B + b] : 0.0f;
+    p.out.padded[e] = real ? 0.0f : 1.0f;
+    p.out.terminated[e] = real ? (p.term_tab[(size_t)t * p.B + b] ? 1.0f : 0.0f) : 1.0f;
+    for (int a = 0; a < p.n; a++) p.out.u[e * p.n + a] = real ? (float)(int)p.u_tab[((size_t)t * p.B + b) * p.n + a] : 0.0f;
+}
+
 thread_local char g_eerr[160] = "";
 
 }  // namespace
@@ -125,6 +183,33 @@ int cs_store_episodes(int B, int T, int n_agents, int n_actions, int obs_w, int 
     hipLaunchKernelGGL(k_episode_small, dim3((unsigned)(((size_t)B * T + 255) / 256)), dim3(256), 0, s, p);
     if (hipGetLastError() != hipSuccess) {
         snprintf(g_eerr, sizeof(g_eerr), "cs_store_episodes: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    return CS_OK;
+}
+
+int cs_store_episodes_compact(int B, int T, int n_agents, int cells, int state_w, const float *map_tab_dev,
+                              const float *s_tab_dev, const int64_t *u_tab_dev, const float *r_tab_dev,
+                              const uint8_t *term_tab_dev, const int64_t *slot_dev, const cs_compact_out *out, void *stream) {
+    if (B < 1 || T < 1 || n_agents < 1 || cells < 1 || state_w < 1 || !map_tab_dev || !s_tab_dev || !u_tab_dev || !r_tab_dev ||
+        !term_tab_dev || !out || !out->map || !out->s_full || !out->u || !out->r || !out->padded || !out->terminated) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_store_episodes_compact: bad argument");
+        return CS_E_ARG;
+    }
+    CompactParams p{B, T, n_agents, cells, state_w, map_tab_dev, s_tab_dev, r_tab_dev, u_tab_dev, term_tab_dev, slot_dev, *out};
+    hipStream_t s = (hipStream_t)stream;
+    int chunks = 1;   // as cs_store_episodes: split the rows when B alone gives fewer than ~2048 blocks
+    while (B * chunks < 2048 && chunks < T + 1) chunks *= 2;
+    const int t_per_block = (T + 1 + chunks - 1) / chunks;
+    const dim3 grid(B, (T + 1 + t_per_block - 1) / t_per_block);
+    const bool vec4 = cells % 4 == 0 && ((uintptr_t)map_tab_dev % 16 == 0) && ((uintptr_t)out->map % 16 == 0);
+    if (vec4)
+        hipLaunchKernelGGL(k_compact_rows<4>, grid, dim3(256), 0, s, p, t_per_block);
+    else
+        hipLaunchKernelGGL(k_compact_rows<1>, grid, dim3(256), 0, s, p, t_per_block);
+    hipLaunchKernelGGL(k_compact_small, dim3((unsigned)(((size_t)B * T + 255) / 256)), dim3(256), 0, s, p);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_store_episodes_compact: kernel launch failed");
         return CS_E_LAUNCH;
     }
     return CS_OK;

@@ -153,7 +153,9 @@ __device__ __forceinline__ void map_build_pass(const DevParams &p, int k, const 
     }
 }
 
-template <int N, int ILP, int BLK = MAP_BLOCK>
+// SNAP (compile time): `obs` is a snapshot table [B][cells] instead of observation rows -- the env's updated map is written
+// ONCE, to obs + b * cells, instead of N times at row stride cells + 4 (map-once episode storage: DESIGN.md section 12).
+template <int N, int ILP, int BLK = MAP_BLOCK, bool SNAP = false>
 __device__ __forceinline__ void map_sweep(const DevParams &p, MapPassLds *s_pass, float *obs, int apply, int parity, int b,
                                           int yblk) {
     const MapJob *job = job_ptr(p, parity, b);
@@ -198,9 +200,13 @@ __device__ __forceinline__ void map_sweep(const DevParams &p, MapPassLds *s_pass
         if ((dirty || reset_pass) && map_update_chunk(p, s_pass, dirty, reset_pass, c, v)) m4[c] = v;
         if (obs) {
             const v4f nv = {v.x, v.y, v.z, v.w};
+            if constexpr (SNAP) {
+                __builtin_nontemporal_store(nv, reinterpret_cast<v4f *>(obs + (size_t)b * p.cells) + c);
+            } else {
 #pragma unroll
-            for (int a = 0; a < N; a++) {  // write-once stream: keep it out of the caches
-                __builtin_nontemporal_store(nv, reinterpret_cast<v4f *>(obs + ((size_t)b * N + a) * row_w) + c);
+                for (int a = 0; a < N; a++) {  // write-once stream: keep it out of the caches
+                    __builtin_nontemporal_store(nv, reinterpret_cast<v4f *>(obs + ((size_t)b * N + a) * row_w) + c);
+                }
             }
         }
     }
@@ -220,6 +226,16 @@ template <int N>
 __global__ __launch_bounds__(MAP_UPD_BLOCK) void k_map_update(DevParams p, int parity) {
     __shared__ MapPassLds s_pass[2];
     map_sweep<N, MAP_UPD_ILP, MAP_UPD_BLOCK>(p, s_pass, nullptr, 1, parity, blockIdx.x, 0);
+}
+
+// The update plus ONE copy of the updated map per env (cs_collect_flight's map table): 1 / N of k_map's write stream, so
+// the sweep is closer to k_map_update's than to k_map's and takes its geometry -- one workgroup per env, every float4 load in flight
+// before the prologue.  `snap` is written for EVERY env: one whose job record carries no pending pass (a frozen, finished
+// env, or apply = 0) skips the prologue and copies its map as it is, as k_map does for the observation rows.
+template <int N>
+__global__ __launch_bounds__(MAP_UPD_BLOCK) void k_map_snap(DevParams p, float *snap, int apply, int parity) {
+    __shared__ MapPassLds s_pass[2];
+    map_sweep<N, MAP_UPD_ILP, MAP_UPD_BLOCK, true>(p, s_pass, snap, apply, parity, blockIdx.x, 0);
 }
 
 // flight rollouts: the map sweep of step t and the kinematics / detection of step t + 1 in ONE launch.  The two do not

@@ -379,6 +379,43 @@ void rollout_policy_flight(const Tensor &cfg, Tensor state, const Tensor &packed
                                 win.data_ptr<uint8_t>(), opt_ptr<float>(obs), opt_ptr<float>(state_out), stream_of(state)));
 }
 
+// flight: rollout_policy_flight without observation rows that also fills the map-once tables (cs_collect_flight):
+// map_tab [T+1, B, cells] and state_tab [T+1, B, S], row 0 = on entry, row t + 1 = after step t
+void collect_flight(const Tensor &cfg, Tensor state, const Tensor &packed, const Tensor &c1w, const Tensor &c1b, const Tensor &c2w,
+                    const Tensor &c2b, const Tensor &lw, const Tensor &lb, Tensor hidden, const Tensor &last, Tensor scratch,
+                    int64_t T, int64_t flags, double epsilon, c10::optional<Tensor> eps_env, double anneal, double min_epsilon,
+                    bool per_step, c10::optional<Tensor> eps_trace, int64_t seed, int64_t step0, int64_t row0, int64_t select,
+                    Tensor actions, Tensor reward, Tensor terminated, Tensor win, Tensor map_tab, Tensor state_tab) {
+    const cs_config &c = config_of(cfg);
+    check_state(c, state);
+    const Shapes s = shapes_of(c);
+    TORCH_CHECK(T >= 1, "coopsearch: T must be >= 1");
+    TORCH_CHECK(c.variant == 1, "coopsearch: collect_flight is for the flight variant");
+    check_f32(packed, "packed", (int64_t)cs_policy_packed_floats(), state);
+    check_f32(c1w, "conv1.weight", 4 * 16, state);
+    check_f32(c1b, "conv1.bias", 4, state);
+    check_f32(c2w, "conv2.weight", 4 * 9, state);
+    check_f32(c2b, "conv2.bias", 1, state);
+    check_f32(lw, "linear.weight", 16 * 576, state);
+    check_f32(lb, "linear.bias", 16, state);
+    check_f32(hidden, "hidden", s.B * s.n * 64, state);
+    check_dev(last, "last", at::kLong, s.B * s.n, state);
+    check_f32(scratch, "scratch", s.B * (16 + 4 * s.n), state);
+    check_dev(actions, "actions", at::kLong, T * s.B * s.n, state);
+    check_dev(reward, "reward", at::kFloat, T * s.B, state);
+    check_dev(terminated, "terminated", at::kByte, T * s.B, state);
+    check_dev(win, "win", at::kByte, T * s.B, state);
+    check_f32(map_tab, "map_tab", (T + 1) * s.B * (s.obs_w - 4), state);
+    check_f32(state_tab, "state_tab", (T + 1) * s.B * s.state_w, state);
+    const cs_epsilon sched = schedule_of(epsilon, eps_env, anneal, min_epsilon, per_step, eps_trace, T, s.B, state);
+    ok(cs_collect_flight(&c, state.data_ptr(), packed.data_ptr<float>(), c1w.data_ptr<float>(), c1b.data_ptr<float>(),
+                         c2w.data_ptr<float>(), c2b.data_ptr<float>(), lw.data_ptr<float>(), lb.data_ptr<float>(),
+                         hidden.data_ptr<float>(), last.data_ptr<int64_t>(), scratch.data_ptr<float>(), (int)T, (int)flags, &sched,
+                         (uint64_t)seed, (uint32_t)step0, (uint64_t)row0, (int)select, actions.data_ptr<int64_t>(),
+                         reward.data_ptr<float>(), terminated.data_ptr<uint8_t>(), win.data_ptr<uint8_t>(),
+                         map_tab.data_ptr<float>(), state_tab.data_ptr<float>(), stream_of(state)));
+}
+
 // common/rollout.py:66-76,105-132 + replay_buffer.py:41-61: step-major tables -> the 11-key episode batch (cs_store_episodes);
 // `outs` in the order o, u, s, r, o_next, s_next, avail_u, avail_u_next, u_onehot, padded, terminated
 void store_episodes(const Tensor &o_tab, const Tensor &s_tab, const Tensor &u_tab, const Tensor &r_tab, const Tensor &term_tab,
@@ -409,6 +446,40 @@ void store_episodes(const Tensor &o_tab, const Tensor &s_tab, const Tensor &u_ta
                                      u_tab.data_ptr<int64_t>(), r_tab.data_ptr<float>(),
                                      reinterpret_cast<const uint8_t *>(term_tab.data_ptr()), opt_ptr<const int64_t>(slots), &eo,
                                      stream_of(o_tab));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
+// the same tables -> the map-once episode keys (cs_store_episodes_compact); `outs` in the order map, s_full, u, r, padded, terminated
+void store_episodes_compact(const Tensor &map_tab, const Tensor &s_tab, const Tensor &u_tab, const Tensor &r_tab,
+                            const Tensor &term_tab, const c10::optional<Tensor> &slots, std::vector<Tensor> outs) {
+    TORCH_CHECK(u_tab.dim() == 3, "coopsearch: u_tab must be [T, B, n]");
+    const int64_t T = u_tab.size(0), B = u_tab.size(1), n = u_tab.size(2);
+    TORCH_CHECK(map_tab.dim() == 3 && s_tab.dim() == 3, "coopsearch: map_tab must be [T+1, B, cells], s_tab [T+1, B, S]");
+    const int64_t cells = map_tab.size(2), S = s_tab.size(2);
+    check_f32(map_tab, "map_tab", (T + 1) * B * cells, map_tab);
+    check_f32(s_tab, "s_tab", (T + 1) * B * S, map_tab);
+    check_dev(u_tab, "u_tab", at::kLong, T * B * n, map_tab);
+    check_f32(r_tab, "r_tab", T * B, map_tab);
+    TORCH_CHECK(term_tab.scalar_type() == at::kByte || term_tab.scalar_type() == at::kBool, "coopsearch: term_tab must be uint8 / bool");
+    check_dev(term_tab, "term_tab", term_tab.scalar_type(), T * B, map_tab);
+    const bool ring = slots.has_value() && slots->defined();
+    if (ring) check_dev(*slots, "slots", at::kLong, B, map_tab);
+    TORCH_CHECK(outs.size() == 6, "coopsearch: store_episodes_compact takes the 6 destination tensors");
+    const int64_t rows[6] = {T + 1, T + 1, T, T, T, T};
+    const int64_t per_slot[6] = {(T + 1) * cells, (T + 1) * S, T * n, T, T, T};
+    float *ptr[6];
+    for (int k = 0; k < 6; k++) {
+        check_f32(outs[k], "episode destination", -1, map_tab);
+        TORCH_CHECK(outs[k].dim() >= 2 && outs[k].size(1) == rows[k] && outs[k].numel() == outs[k].size(0) * per_slot[k] &&
+                        outs[k].size(0) >= (ring ? 1 : B),
+                    "coopsearch: compact episode destination ", k, " must be [slots, T (+ 1), ...] of the episode shape");
+        ptr[k] = outs[k].data_ptr<float>();
+    }
+    const cs_compact_out co{ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], ptr[5]};
+    const int rc = cs_store_episodes_compact((int)B, (int)T, (int)n, (int)cells, (int)S, map_tab.data_ptr<float>(),
+                                             s_tab.data_ptr<float>(), u_tab.data_ptr<int64_t>(), r_tab.data_ptr<float>(),
+                                             reinterpret_cast<const uint8_t *>(term_tab.data_ptr()), opt_ptr<const int64_t>(slots), &co,
+                                             stream_of(map_tab));
     TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
 }
 
@@ -501,6 +572,13 @@ TORCH_LIBRARY(coopsearch, m) {
           "Tensor(g!)? obs, Tensor(h!)? state_out) -> ()", &rollout_policy_flight);
     m.def("store_episodes(Tensor o_tab, Tensor s_tab, Tensor u_tab, Tensor r_tab, Tensor term_tab, Tensor? slots, int n_actions, "
           "Tensor(a!)[] outs) -> ()", &store_episodes);
+    m.def("collect_flight(Tensor cfg, Tensor(a!) state, Tensor packed, Tensor c1w, Tensor c1b, Tensor c2w, Tensor c2b, "
+          "Tensor lw, Tensor lb, Tensor(b!) hidden, Tensor last, Tensor(i!) scratch, int T, int flags, float epsilon, "
+          "Tensor(j!)? eps_env, float anneal, float min_epsilon, bool per_step, Tensor(k!)? eps_trace, int seed, "
+          "int step0, int row0, int select, Tensor(c!) actions, Tensor(d!) reward, Tensor(e!) terminated, Tensor(f!) win, "
+          "Tensor(g!) map_tab, Tensor(h!) state_tab) -> ()", &collect_flight);
+    m.def("store_episodes_compact(Tensor map_tab, Tensor s_tab, Tensor u_tab, Tensor r_tab, Tensor term_tab, Tensor? slots, "
+          "Tensor(a!)[] outs) -> ()", &store_episodes_compact);
     m.def("gru_seq_forward(Tensor w_hh, Tensor b_hh, Tensor gi, Tensor? h0, int T, int rows, Tensor(a!) h_out, "
           "Tensor(b!)? saved_out) -> ()", &gru_seq_forward);
     m.def("gru_seq_backward(Tensor w_hh, Tensor dh_seq, Tensor h_seq, Tensor? h0, Tensor saved, int T, int rows, "

@@ -448,6 +448,65 @@ class BatchedFlightEnv:
         out["win"] = out["win"].view(torch.bool)
         return out
 
+    def collect_flight(self, agents, T, epsilon=0.0, evaluate=True, out=None, update_views=True, eps_env=None, anneal=0.0,
+                       min_epsilon=0.0, per_step=False, eps_trace=None):
+        """flight: `rollout_policy(emit=False)` that also records what an episode batch needs, every map ONCE
+        (cs_collect_flight).  Returns the `rollout_policy` dict without obs / state, plus
+        `map` float32 [T+1, B, cells] and `state` float32 [T+1, B, S]: row 0 on entry, row t + 1 after step t.  Actions,
+        rewards, flags, the hidden state and the carried epsilon are those of `rollout_policy`, bit for bit; no tensor of
+        n * cells floats per step is allocated or written.  `out` reuses caller buffers (keys actions / reward / terminated /
+        win / map / state); the schedule arguments are `rollout_policy`'s."""
+        if not self.flight:
+            raise ValueError("collect_flight: the flight variant only (flight_easy observations carry no map)")
+        T = int(T)
+        B, n, dev = self.batch, self.n_agents, self.device
+        if agents.rows != B * n or not bool(getattr(agents, "conv", False)):
+            raise ValueError("collect_flight: `agents` must be a FusedAgents with the conv front end for this env's batch")
+        out = dict(out) if out else {}
+        spec = dict(reward=((T, B), torch.float32), terminated=((T, B), torch.uint8), win=((T, B), torch.uint8),
+                    actions=((T, B, n), torch.int64), map=((T + 1, B, self.cells), torch.float32),
+                    state=((T + 1, B, self.state_shape), torch.float32))
+        for k, (shape, dt) in spec.items():
+            if out.get(k) is None:
+                out[k] = torch.empty(shape, dtype=dt, device=dev)
+            elif out[k].numel() * out[k].element_size() != torch.Size(shape).numel() * dt.itemsize or not out[k].is_contiguous():
+                raise ValueError(f"collect_flight(out=): bad destination for {k!r}")
+        flags = (_lib.FREEZE_DONE if self.freeze_done else 0) | (_lib.AUTO_RESET if self.auto_reset else 0)
+        sel_eps, sel_flags = agents.selection(epsilon, evaluate)
+        if evaluate and not agents.softmax:
+            eps_env = eps_trace = None   # epsilon = 0 if evaluate (rollout.py:35): no schedule
+        if eps_trace is not None and eps_env is None:
+            raise ValueError("collect_flight: eps_trace needs eps_env")
+        for name, tns, numel in (("eps_env", eps_env, B), ("eps_trace", eps_trace, T * B)):
+            if tns is not None and (tns.dtype != torch.float64 or tns.numel() != numel or not tns.is_contiguous() or not tns.is_cuda
+                                    or (tns.device.index or 0) != (dev.index or 0)):
+                raise ValueError(f"collect_flight: {name} must be a contiguous float64 device tensor of {numel} elements")
+        scratch = getattr(agents, "_flight_scratch", None)
+        if scratch is None or scratch.numel() != B * (16 + 4 * n):
+            scratch = agents._flight_scratch = torch.empty(B, 16 + 4 * n, dtype=torch.float32, device=dev)
+        term, win = out["terminated"].view(torch.uint8), out["win"].view(torch.uint8)
+        if self._ops is not None:
+            self._ops.collect_flight(self._cfg_t, self._blob, agents.packed, *agents.conv_w, agents.hidden, agents.actions, scratch,
+                                     T, flags, sel_eps, eps_env, float(anneal), float(min_epsilon), bool(per_step), eps_trace,
+                                     agents.seed, agents.calls, agents.row0, sel_flags, out["actions"], out["reward"], term, win,
+                                     out["map"], out["state"])
+        else:
+            sched_c = _lib.CsEpsilon(sel_eps, float(anneal), float(min_epsilon), 1 if per_step else 0, 0,
+                                     eps_env.data_ptr() if eps_env is not None else None,
+                                     eps_trace.data_ptr() if eps_trace is not None else None)
+            self._call(self._L.cs_collect_flight,
+                self._cfgp, self._blob.data_ptr(), agents.packed.data_ptr(), *[w.data_ptr() for w in agents.conv_w],
+                agents.hidden.data_ptr(), agents.actions.data_ptr(), scratch.data_ptr(), T, flags, C.byref(sched_c), agents.seed,
+                agents.calls, agents.row0, sel_flags, out["actions"].data_ptr(), out["reward"].data_ptr(), term.data_ptr(),
+                win.data_ptr(), out["map"].data_ptr(), out["state"].data_ptr(), self._stream())
+        agents.calls += T
+        agents.actions.copy_(out["actions"][-1])
+        if update_views:
+            self.refresh()
+        out["terminated"] = term.view(torch.bool)
+        out["win"] = win.view(torch.bool)
+        return out
+
     def refresh(self):
         """Re-emit get_obs()/get_state() from the device state (after editing raw())."""
         if self._ops is not None:

@@ -17,6 +17,10 @@ learner's checkpoints load into the reference.
 recursion over t of the returns (DOP's TD(lambda) critic target, REINFORCE's discounted return), is one HIP launch
 (`episode_returns`: cs_episode_returns, csrc/returns.h); DOP's critic, the mixers and the action-probability head run once
 over all rows in torch.
+
+Every `learn` also takes a batch in the map-once format of the flight variant (replay.COMPACT_KEYS) as
+it is.  QMIX and REINFORCE never build `o` / `o_next` from it: the conv front end runs once per (episode, step) on the map
+(`map_features`), its 16 features are broadcast over the agents, and the rest of the unroll is the one above.
 """
 import os
 
@@ -25,6 +29,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .agents import AgentRNN, rnn_input_shape
+from .replay import expand_compact
 
 HIDDEN = 64   # rnn_hidden_dim: the recurrence kernels are built for it (get_mixer_args, common/arguments.py:58)
 
@@ -95,16 +100,30 @@ class GRUSequence(torch.autograd.Function):
         return (dgi if need_gi else None), dw, db, dh0
 
 
-def unroll_q(net, X, h0=None, impl="fused"):
+def map_features(net, maps):
+    """The conv front end of AgentRNN.forward on maps [..., cells] -> [..., conv_out_dim]: the same modules, one row per map."""
+    a = net.args
+    prob = maps.reshape(-1, 1, a.map_size, a.map_size)
+    feat = net.linear(net.conv(prob).reshape(-1, a.dim_2 * net.conv_size ** 2))
+    return feat.view(*maps.shape[:-1], -1)
+
+
+def unroll_q(net, X, h0=None, impl="fused", featured=False):
     """Q-values of all T steps: X [T, R, in] (rows of get_inputs, policy/qmix.py:132-158), h0 [R, 64] or None (zeros) ->
     q [T, R, n_actions].  impl "fused": the conv front end (flight), fc1 and the input projection over all T*R rows at once,
-    GRUSequence, then fc2 over all rows; "torch": the reference's loop of net(x_t, h) over t (get_q_values)."""
+    GRUSequence, then fc2 over all rows; "torch": the reference's loop of net(x_t, h) over t (get_q_values).
+    featured: the rows of X already carry the conv features in place of the map (compact_actor_inputs): the front end is
+    skipped, the rest is the same."""
     T, R = int(X.shape[0]), int(X.shape[1])
     if impl == "torch":
         h = h0 if h0 is not None else X.new_zeros(R, net.args.rnn_hidden_dim)
         qs = []
         for t in range(T):
-            q, h = net(X[t], h)
+            if featured:   # AgentRNN.forward behind its front end
+                h = net.rnn(F.relu(net.fc1(X[t])), h)
+                q = net.fc2(h)
+            else:
+                q, h = net(X[t], h)
             qs.append(q)
         return torch.stack(qs, 0)
     if impl != "fused":
@@ -112,7 +131,7 @@ def unroll_q(net, X, h0=None, impl="fused"):
     if net.args.rnn_hidden_dim != HIDDEN:
         raise ValueError(f"the fused unroll is built for rnn_hidden_dim = {HIDDEN}")
     x = X.reshape(T * R, -1)
-    if net.args.conv:   # the same modules on the same maps as AgentRNN.forward, all T*R maps in one call
+    if net.args.conv and not featured:   # the same modules on the same maps as AgentRNN.forward, all T*R maps in one call
         cells = net.args.map_size ** 2
         prob = x[:, :cells].reshape(-1, 1, net.args.map_size, net.args.map_size)
         feat = net.linear(net.conv(prob).reshape(-1, net.args.dim_2 * net.conv_size ** 2))
@@ -181,8 +200,8 @@ def soft_update(pairs, tau):
 def device_batch(batch, device, max_episode_len=None):
     """A sampled (or freshly collected) batch dict on `device`, every key cut to max_episode_len steps (what agent.py:112-122
     does before calling learn; None = the full T)."""
-    if max_episode_len is not None:
-        batch = {k: v[:, :max_episode_len] for k, v in batch.items()}
+    if max_episode_len is not None:   # (a compact batch keeps one more row of map / s_full: the step after the last)
+        batch = {k: v[:, :max_episode_len + (1 if k in ("map", "s_full") else 0)] for k, v in batch.items()}
     return {k: torch.as_tensor(v, device=device) for k, v in batch.items()}
 
 
@@ -203,6 +222,39 @@ def actor_inputs(args, n_agents, batch, T):
     X = torch.cat(parts, 3).transpose(0, 1).reshape(T, E * n, -1)
     X_next = torch.cat(parts_next, 3).transpose(0, 1).reshape(T, E * n, -1)
     return X, X_next
+
+
+def compact_actor_inputs(args, n_agents, batch, net, net_next=None):
+    """actor_inputs for a map-once batch that has been through `with_narrow_keys`, without `o` / `o_next`: rows are
+    conv features ++ own 4 floats ++ one-hot ++ agent id, [T, E*n, 16 + 4 + A + n] -- what AgentRNN.forward makes of
+    actor_inputs' rows behind its conv front end.  The front end runs once per (episode, step): `net`'s on map[:, :T] * real
+    (with a graph when gradients are on), `net_next`'s (the target network; None: no X_next) on map[:, 1:] * real, both
+    broadcast over the agents."""
+    if not (getattr(args, "last_action", True) and getattr(args, "reuse_network", True)):
+        raise ValueError("a map-once batch needs last_action and reuse_network (the reference's defaults)")
+    m, sf, u_onehot = batch["map"], batch["s_full"], batch["u_onehot"]
+    E, T, n = int(u_onehot.shape[0]), int(u_onehot.shape[1]), n_agents
+    real = 1 - batch["padded"]                                       # [E, T, 1]
+    real4 = real.unsqueeze(-1)
+    own = sf[..., :4 * n].reshape(E, T + 1, n, 4)                    # emit<N>: state[4i..4i+3] is agent i's observation tail
+    ids = torch.eye(n, device=m.device, dtype=m.dtype).expand(E, T, n, n)
+
+    def rows(front, lo, last):
+        feat = map_features(front, m[:, lo:lo + T] * real).unsqueeze(2).expand(E, T, n, -1)
+        return torch.cat([feat, own[:, lo:lo + T] * real4, last, ids], 3).transpose(0, 1).reshape(T, E * n, -1)
+    X = rows(net, 0, torch.cat([torch.zeros_like(u_onehot[:, :1]), u_onehot[:, :-1]], 1))
+    if net_next is None:
+        return X, None
+    with torch.no_grad():
+        return X, rows(net_next, 1, u_onehot)
+
+
+def with_narrow_keys(batch, n_agents, n_actions):
+    """A map-once batch plus the dense keys that do not repeat the map (s, s_next, avail_u, avail_u_next, u_onehot: by
+    expand_compact's definition); a dense batch as it is."""
+    if "map" not in batch:
+        return batch
+    return {**batch, **expand_compact(batch, n_agents, n_actions, wide=False)}
 
 
 class QMixLearner:
@@ -254,27 +306,32 @@ class QMixLearner:
 
     def get_q_values(self, batch, T):
         """(q_evals, q_targets) [E, T, n, n_actions] (qmix.py:160-182); the target network runs without a graph."""
-        E, n = int(batch["o"].shape[0]), self.n_agents
-        X, X_next = self.get_inputs(batch, T)
+        E, n = int(batch["u"].shape[0]), self.n_agents
+        featured = "map" in batch   # map-once: the front end once per (episode, step), eval on row t, target on row t + 1
+        if featured:
+            X, X_next = compact_actor_inputs(self.args, n, batch, self.eval_rnn, self.target_rnn)
+        else:
+            X, X_next = self.get_inputs(batch, T)
         self.init_hidden(E)
-        q_eval = unroll_q(self.eval_rnn, X, None, self.unroll)
+        q_eval = unroll_q(self.eval_rnn, X, None, self.unroll, featured)
         with torch.no_grad():
-            q_target = unroll_q(self.target_rnn, X_next, None, self.unroll)
+            q_target = unroll_q(self.target_rnn, X_next, None, self.unroll, featured)
         shape = (T, E, n, self.n_actions)
         return q_eval.view(shape).transpose(0, 1), q_target.view(shape).transpose(0, 1)
 
     def learn(self, batch, max_episode_len=None, train_step=0, epsilon=None):
         """One QMIX update (qmix.py:85-130) on a DeviceReplayBuffer.sample() dict as it is ([E, T, ...] float32; `u` is cast to
-        long).  max_episode_len: cut every key to that many steps (what agent.py:112-122 does before calling learn); None = the
+        long), or on a CompactReplayBuffer.sample() dict (the map-once keys; `o` / `o_next` are never built).  max_episode_len: cut every key to that many steps (what agent.py:112-122 does before calling learn); None = the
         full T, which is what the reference's _get_max_episode_len amounts to (it never shortens T).  Returns the loss (a device
         tensor: no host synchronisation)."""
-        batch = device_batch(batch, self.device, max_episode_len)
-        T = int(batch["o"].shape[1])
+        batch = with_narrow_keys(device_batch(batch, self.device, max_episode_len), self.n_agents, self.n_actions)
+        T = int(batch["u"].shape[1])
         u = batch["u"].long()
-        s, s_next, r = batch["s"].float(), batch["s_next"].float(), batch["r"].float()
-        avail_u_next, terminated = batch["avail_u_next"], batch["terminated"].float()
-        batch = {k: (v.float() if k in ("o", "o_next", "u_onehot") else v) for k, v in batch.items()}
-        mask = 1 - batch["padded"].float()
+        dt = self.eval_rnn.fc1.weight.dtype   # float32, unless the caller converted the networks
+        s, s_next, r = batch["s"].to(dt), batch["s_next"].to(dt), batch["r"].to(dt)
+        avail_u_next, terminated = batch["avail_u_next"], batch["terminated"].to(dt)
+        batch = {k: (v.to(dt) if k in ("o", "o_next", "u_onehot", "map", "s_full", "padded") else v) for k, v in batch.items()}
+        mask = 1 - batch["padded"]
 
         q_evals, q_targets = self.get_q_values(batch, T)
         q_evals = torch.gather(q_evals, dim=3, index=u).squeeze(3)
@@ -440,16 +497,19 @@ def td_lambda_torch(r, terminated, padded, q, gamma, td_lambda):
 def _policy_logits(net, args, n_agents, batch, T, impl):
     """The actor's outputs [E, T, n, A] over all T steps: actor_inputs' X through unroll_q (the fused recurrence, or the
     reference's step loop)."""
-    E = int(batch["o"].shape[0])
-    X, _ = actor_inputs(args, n_agents, batch, T)
-    return unroll_q(net, X, None, impl).view(T, E, n_agents, -1).transpose(0, 1)
+    E = int(batch["u"].shape[0])
+    featured = "map" in batch   # map-once: the front end once per (episode, step)
+    X = compact_actor_inputs(args, n_agents, batch, net)[0] if featured else actor_inputs(args, n_agents, batch, T)[0]
+    return unroll_q(net, X, None, impl, featured).view(T, E, n_agents, -1).transpose(0, 1)
 
 
-def _prepare(batch, device, max_episode_len):
-    """device_batch, then the reference's conversion (u -> long, everything else float32) -> (batch, T, u, mask [E, T, 1])."""
+def _prepare(batch, device, max_episode_len, n_agents, n_actions, dtype=torch.float32):
+    """device_batch, then the reference's conversion (u -> long, everything else float32: `dtype`, the networks') ->
+    (batch, T, u, mask [E, T, 1]).  A map-once batch gains the narrow dense keys (with_narrow_keys), never o / o_next."""
     batch = device_batch(batch, device, max_episode_len)
-    batch = {k: (v.long() if k == "u" else v.float()) for k, v in batch.items()}
-    return batch, int(batch["o"].shape[1]), batch["u"], 1 - batch["padded"]
+    batch = {k: (v.long() if k == "u" else v.to(dtype)) for k, v in batch.items()}
+    batch = with_narrow_keys(batch, n_agents, n_actions)
+    return batch, int(batch["u"].shape[1]), batch["u"], 1 - batch["padded"]
 
 
 class DOPLearner:
@@ -496,7 +556,11 @@ class DOPLearner:
         soft_update(((self.eval_critic, self.target_critic), (self.eval_mixer_net, self.target_mixer_net)), self.tau)
 
     def critic_inputs(self, batch):
-        """_get_critic_inputs (dop.py:269-310) for all steps: s ++ o ++ agent id and s_next ++ o_next ++ id, [E, T, n, in]."""
+        """_get_critic_inputs (dop.py:269-310) for all steps: s ++ o ++ agent id and s_next ++ o_next ++ id, [E, T, n, in].
+        The critic reads the raw map as inputs, so a map-once batch is expanded here (expand_compact), for the critic only:
+        the actor goes through compact_actor_inputs."""
+        if "map" in batch:
+            batch = {**batch, **expand_compact(batch, self.n_agents, self.n_actions)}
         o = batch["o"]
         E, T, n = int(o.shape[0]), int(o.shape[1]), self.n_agents
         ids = torch.eye(n, device=o.device, dtype=o.dtype).expand(E, T, n, n)
@@ -525,12 +589,12 @@ class DOPLearner:
         return td_lambda_torch(batch["r"], batch["terminated"], batch["padded"], q_total_target, a.gamma, a.td_lambda)
 
     def learn(self, batch, max_episode_len=None, train_step=0, epsilon=0.0):
-        """One DOP update (dop.py:89-130) on a DeviceReplayBuffer.sample() dict as it is: the critic and mixer step (its TD(lambda)
+        """One DOP update (dop.py:89-130) on a DeviceReplayBuffer.sample() dict (or a CompactReplayBuffer's) as it is: the critic and mixer step (its TD(lambda)
         loss, one clip over both, soft update), then the actor step with the advantage of the critic's q-values from BEFORE its
         step (dop.py:161).  max_episode_len: as QMixLearner.learn; epsilon: a float or a 0-dim device tensor.  Returns
         (critic_loss, actor_loss) as device tensors (no host synchronisation); the pre-clip norms are last_critic_grad_norm and
         last_actor_grad_norm."""
-        batch, T, u, mask1 = _prepare(batch, self.device, max_episode_len)
+        batch, T, u, mask1 = _prepare(batch, self.device, max_episode_len, self.n_agents, self.n_actions, self.actor.fc1.weight.dtype)
         E, n = int(u.shape[0]), self.n_agents
         mask = mask1.expand(E, T, n)
         s, s_next = batch["s"], batch["s_next"]
@@ -607,9 +671,9 @@ class ReinforceLearner:
         return returns_torch(batch["r"], batch["terminated"], batch["padded"], self.args.gamma)
 
     def learn(self, batch, max_episode_len=None, train_step=0, epsilon=0.0):
-        """One REINFORCE update (reinforce.py:63-99): loss = -sum(R log pi(u) m) / sum(m), Adam or RMSprop, no gradient clipping
+        """One REINFORCE update (reinforce.py:63-99) on a dense or a map-once episode dict: loss = -sum(R log pi(u) m) / sum(m), Adam or RMSprop, no gradient clipping
         (reinforce.py:97 has it commented out).  Returns the loss as a device tensor (no host synchronisation)."""
-        batch, T, u, mask1 = _prepare(batch, self.device, max_episode_len)
+        batch, T, u, mask1 = _prepare(batch, self.device, max_episode_len, self.n_agents, self.n_actions, self.eval_rnn.fc1.weight.dtype)
         E, n = int(u.shape[0]), self.n_agents
         mask = mask1.expand(E, T, n)
         n_return = self.get_returns(batch).unsqueeze(2).expand(E, T, n)

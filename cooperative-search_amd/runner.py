@@ -23,12 +23,12 @@ import torch
 from .agents import FusedAgents
 from .collector import EpisodeCollector, EpsilonSchedule
 from .learner import DOPLearner, QMixLearner, ReinforceLearner
-from .replay import KEYS, DeviceReplayBuffer
+from .replay import CompactReplayBuffer, DeviceReplayBuffer
 
 # fields the reference's get_mixer_args / get_common_args set and this package's get_*_args leave to the caller
 # (common/arguments.py:43-46, :84-104)
 RUN_DEFAULTS = dict(n_epoch=500000, n_episodes=1, train_steps=1, evaluate_cycle=200, save_cycle=500, evaluate_epoch=20,
-                    model_dir="./model/", result_dir="./result/", load_model=False)
+                    model_dir="./model/", result_dir="./result/", load_model=False, compact_episodes=False)
 LEARNERS = {"qmix": QMixLearner, "dop": DOPLearner, "reinforce": ReinforceLearner}
 # the checkpoint file whose presence get_model_idx() - 1 must show when resuming (the reference learners' __init__)
 _RESUME = {"qmix": ("rnn", "qmix"), "dop": ("actor", "critic", "mixer"), "reinforce": ("rnn",)}
@@ -63,7 +63,9 @@ def apply_run_defaults(args):
 class Runner:
     """Runner(env, args): `env` a BatchedFlightEnv; `args` the reference's namespace after get_mixer_args / get_dop_args /
     get_reinforce_args and apply_env_info; args.alg selects the learner.  The parts (learner, agents, schedule, collector,
-    buffer) are built here unless passed in."""
+    buffer) are built here unless passed in.  args.compact_episodes (flight only; default False): episodes are collected,
+    stored and learnt from in the map-once format (replay.COMPACT_KEYS) -- a CompactReplayBuffer and
+    generate_episodes(compact=True); the schedule of calls is the same."""
 
     def __init__(self, env, args, learner=None, agents=None, schedule=None, collector=None, buffer=None):
         alg = getattr(args, "alg", None)
@@ -89,7 +91,10 @@ class Runner:
         self.collector = collector if collector is not None else EpisodeCollector(env, self.schedule)
         self.buffer = None
         if args.off_policy:
-            self.buffer = buffer if buffer is not None else DeviceReplayBuffer(args, args.buffer_size, device)
+            ring = CompactReplayBuffer if args.compact_episodes else DeviceReplayBuffer
+            self.buffer = buffer if buffer is not None else ring(args, args.buffer_size, device)
+        # generate_episodes' format switch; nothing is passed for the dense format, so a collector without it keeps working
+        self._collect_kw = dict(compact=True) if args.compact_episodes else {}
         self.win_rates, self.targets_find, self.episode_rewards = [], [], []
         self.result_path = args.result_dir + run_name(args)
         os.makedirs(self.result_path, exist_ok=True)   # runner.py:33-39
@@ -115,14 +120,15 @@ class Runner:
         a = self.args
         if a.off_policy:
             for idx in range(a.n_episodes):
-                self.collector.generate_episodes(agents=self.agents, evaluate=False, episode_num=idx, into=self.buffer)
+                self.collector.generate_episodes(agents=self.agents, evaluate=False, episode_num=idx, into=self.buffer,
+                                                 **self._collect_kw)
             for _ in range(a.train_steps):
                 self.train(self.buffer.sample(min(self.buffer.current_size, a.batch_size)), train_steps)
                 train_steps += 1
         else:
-            eps = [self.collector.generate_episodes(agents=self.agents, evaluate=False, episode_num=idx)[0]
+            eps = [self.collector.generate_episodes(agents=self.agents, evaluate=False, episode_num=idx, **self._collect_kw)[0]
                    for idx in range(a.n_episodes)]
-            batch = eps[0] if len(eps) == 1 else {k: torch.cat([e[k] for e in eps], 0) for k in KEYS}
+            batch = eps[0] if len(eps) == 1 else {k: torch.cat([e[k] for e in eps], 0) for k in eps[0]}
             self.train(batch, train_steps)
             train_steps += 1
         return train_steps

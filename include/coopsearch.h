@@ -37,8 +37,9 @@ extern "C" {
                               4: cs_source_hash, CS_KERNEL_OCT; 5: CS_KERNEL_ODE; 6: cs_epsilon (exploration schedule),
                               cs_epsilon_step, CS_KERNEL_LANEV; 7: CS_CHECK_ACTIONS, cs_has_legacy_kernels;
                               still 7: cs_gru_seq_forward, cs_gru_seq_backward, cs_learn_last_error were ADDED, then
-                              cs_episode_returns, then cs_policy_pack_device (no existing export or struct changed: a
-                              version-7 caller works unchanged) */
+                              cs_episode_returns, then cs_policy_pack_device, then cs_collect_flight, cs_compact_out and
+                              cs_store_episodes_compact (no existing export or struct changed: a version-7 caller works
+                              unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
 #define CS_MAX_MAP 64
@@ -349,6 +350,21 @@ int cs_rollout_policy_flight(const cs_config *cfg, void *state_dev, const float 
                              int select, int64_t *actions_dev, float *reward_dev, uint8_t *terminated_dev, uint8_t *win_dev,
                              float *obs_dev, float *state_out_dev, void *stream);
 
+/* cs_rollout_policy_flight with obs_dev == NULL that ALSO records what an episode batch needs, each map once (map-once
+ * episode storage): all agents of an env observe the same map, and step t's o_next is step t + 1's o.
+ *   map_tab_dev    float [T+1][B][map*map]  row 0: every env's probability map on entry; row t + 1: after step t (written
+ *                  by the step's map sweep beside its update, one 16-byte-wide copy per env; 16-byte aligned)
+ *   state_tab_dev  float [T+1][B][4n+3m]    row 0: get_state() on entry; row t + 1: after step t
+ * Both tables are written for EVERY env and row, a frozen, finished env included (its rows repeat).  The agents' own 4
+ * observation floats are not recorded: they are state[4i..4i+3] of the same instant (one float4 written to both places).
+ * Actions, rewards, flags, hidden state and the carried epsilon are cs_rollout_policy_flight's, bit for bit. */
+int cs_collect_flight(const cs_config *cfg, void *state_dev, const float *packed_dev, const float *conv1_w_dev,
+                      const float *conv1_b_dev, const float *conv2_w_dev, const float *conv2_b_dev, const float *lin_w_dev,
+                      const float *lin_b_dev, float *hidden_dev, const int64_t *last_dev, float *scratch_dev, int T, int flags,
+                      const cs_epsilon *eps, uint64_t seed, uint32_t step0, uint64_t row0, int select, int64_t *actions_dev,
+                      float *reward_dev, uint8_t *terminated_dev, uint8_t *win_dev, float *map_tab_dev, float *state_tab_dev,
+                      void *stream);
+
 /* ---- caller-side rows f1 / f2: episode batch assembly ------------------------------------------------------------
  * common/rollout.py:66-76,105-132 (the eleven per-episode arrays and their padding: steps after termination are zero
  * rows with padded = 1, terminated = 1) and common/replay_buffer.py:41-61 (store_episode) in one pass over the
@@ -362,6 +378,19 @@ typedef struct cs_episode_out {
 int cs_store_episodes(int B, int T, int n_agents, int n_actions, int obs_w, int state_w, const float *o_tab_dev,
                       const float *s_tab_dev, const int64_t *u_tab_dev, const float *r_tab_dev,
                       const uint8_t *term_tab_dev, const int64_t *slot_dev, const cs_episode_out *out, void *stream);
+/* The same episodes in the map-once format (cs_collect_flight's tables -> a fresh batch or ring slots): float32
+ *   map [slots][T+1][cells]   s_full [slots][T+1][state_w]   u [slots][T][n]   r / padded / terminated [slots][T]
+ * With L the number of real (un-padded) steps of an episode, rows t <= L of map / s_full are the tables' rows and rows
+ * t > L are zero; u, r, padded, terminated are cs_store_episodes' keys of the same names.  One pass over the wide keys,
+ * 16-byte pieces where the rows' alignment allows.
+ *   map_tab [T+1][B][cells]   s_tab [T+1][B][state_w]   u_tab int64 [T][B][n]   r_tab [T][B]   term_tab u8 [T][B] */
+typedef struct cs_compact_out {
+    float *map, *s_full, *u, *r, *padded, *terminated;
+} cs_compact_out;
+
+int cs_store_episodes_compact(int B, int T, int n_agents, int cells, int state_w, const float *map_tab_dev,
+                              const float *s_tab_dev, const int64_t *u_tab_dev, const float *r_tab_dev,
+                              const uint8_t *term_tab_dev, const int64_t *slot_dev, const cs_compact_out *out, void *stream);
 const char *cs_episodes_last_error(void);
 
 /* ---- QMIX learner: the GRU recurrence of the agent network over T steps, forward and backward ---------------------
