@@ -406,6 +406,8 @@ __global__ __launch_bounds__(PBLOCK, 4) void k_conv_features(ConvParams p) {
 #undef CONV_FETCH
 }
 
+#include "conv_bwd.h"
+
 // ---- cs_policy_pack on the device (cs_policy_pack_device): the learner's parameters -> the packed blob, no host round trip -----
 // ONE workgroup (inputs and blob are ~129 KB each).  Range pass: every weight entry in cs_policy_pack's check order (fc1.weight,
 // rnn.weight_ih, rnn.weight_hh, fc2.0.weight, fc2.2.weight; flat index within each) is tested with the host's predicate
@@ -635,6 +637,57 @@ int cs_policy_conv_features(const float *conv1_w_dev, const float *conv1_b_dev, 
     hipLaunchKernelGGL(k_conv_features, dim3(n_maps < resident ? n_maps : resident), dim3(PBLOCK), 0, (hipStream_t)stream, p);
     if (hipGetLastError() != hipSuccess) {
         snprintf(g_perr, sizeof(g_perr), "cs_policy_conv_features: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    return CS_OK;
+}
+
+// The backward of cs_policy_conv_features: the six weight gradients summed over the maps (conv_bwd.h).  Two launches, no
+// atomics: one partial set per workgroup into scratch_dev, then a fixed-order sum.
+static int conv_bwd_grid(int n_maps) {
+    static const int resident = resident_blocks(k_conv_features_bwd);
+    return n_maps < resident ? n_maps : resident;
+}
+
+int cs_policy_conv_features_backward_scratch(int n_maps, int64_t *floats_out) {
+    if (n_maps < 1 || !floats_out) {
+        snprintf(g_perr, sizeof(g_perr), "cs_policy_conv_features_backward_scratch: bad argument (n_maps = %d)", n_maps);
+        return CS_E_ARG;
+    }
+    *floats_out = (int64_t)conv_bwd_grid(n_maps) * CG_STRIDE;
+    return CS_OK;
+}
+
+int cs_policy_conv_features_backward(const float *conv1_w_dev, const float *conv1_b_dev, const float *conv2_w_dev,
+                                     const float *conv2_b_dev, const float *lin_w_dev, const float *lin_b_dev,
+                                     const float *maps_dev, int64_t map_stride, int n_maps, const float *dfeat_dev,
+                                     float *d_conv1_w_dev, float *d_conv1_b_dev, float *d_conv2_w_dev, float *d_conv2_b_dev,
+                                     float *d_lin_w_dev, float *d_lin_b_dev, float *scratch_dev, int64_t scratch_floats,
+                                     void *stream) {
+    if (!conv1_w_dev || !conv1_b_dev || !conv2_w_dev || !conv2_b_dev || !lin_w_dev || !lin_b_dev || !maps_dev || !dfeat_dev ||
+        !d_conv1_w_dev || !d_conv1_b_dev || !d_conv2_w_dev || !d_conv2_b_dev || !d_lin_w_dev || !d_lin_b_dev || !scratch_dev ||
+        n_maps < 1) {
+        snprintf(g_perr, sizeof(g_perr), "cs_policy_conv_features_backward: bad argument (n_maps = %d; no pointer may be null)", n_maps);
+        return CS_E_ARG;
+    }
+    const int grid = conv_bwd_grid(n_maps);
+    if (scratch_floats < (int64_t)grid * CG_STRIDE) {
+        snprintf(g_perr, sizeof(g_perr), "cs_policy_conv_features_backward: scratch holds %lld floats, %lld needed "
+                 "(cs_policy_conv_features_backward_scratch)", (long long)scratch_floats, (long long)grid * CG_STRIDE);
+        return CS_E_ARG;
+    }
+    const int vec4 = ((uintptr_t)maps_dev % 16 == 0) && (map_stride % 4 == 0);
+    const ConvBwdParams p{{conv1_w_dev, conv1_b_dev, conv2_w_dev, conv2_b_dev, lin_w_dev, lin_b_dev, maps_dev, (long long)map_stride,
+                           n_maps, vec4, nullptr}, dfeat_dev, scratch_dev};
+    hipLaunchKernelGGL(k_conv_features_bwd, dim3(grid), dim3(PBLOCK), 0, (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_perr, sizeof(g_perr), "cs_policy_conv_features_backward: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    const ConvReduceParams r{scratch_dev, grid, d_conv1_w_dev, d_conv1_b_dev, d_conv2_w_dev, d_conv2_b_dev, d_lin_w_dev, d_lin_b_dev};
+    hipLaunchKernelGGL(k_conv_grad_reduce, dim3((CG_FLOATS + 63) / 64), dim3(256), 0, (hipStream_t)stream, r);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_perr, sizeof(g_perr), "cs_policy_conv_features_backward: reduction launch failed");
         return CS_E_LAUNCH;
     }
     return CS_OK;

@@ -262,6 +262,44 @@ void policy_conv_features(const Tensor &c1w, const Tensor &c1b, const Tensor &c2
     TORCH_CHECK(rc == CS_OK, cs_policy_last_error());
 }
 
+// the learners' backward of policy_conv_features (cs_policy_conv_features_backward): dfeat [n_maps, 16] -> the six weight
+// gradients, written; scratch: float32, at least policy_conv_features_backward_scratch(n_maps) elements
+int64_t policy_conv_features_backward_scratch(int64_t n_maps) {
+    int64_t floats = 0;
+    TORCH_CHECK(n_maps >= 1 && n_maps <= INT32_MAX, "coopsearch: n_maps must be 1 .. 2^31 - 1");
+    const int rc = cs_policy_conv_features_backward_scratch((int)n_maps, &floats);
+    TORCH_CHECK(rc == CS_OK, cs_policy_last_error());
+    return floats;
+}
+
+void policy_conv_features_backward(const Tensor &c1w, const Tensor &c1b, const Tensor &c2w, const Tensor &c2b, const Tensor &lw,
+                                   const Tensor &lb, const Tensor &maps, int64_t map_stride, int64_t n_maps, const Tensor &dfeat,
+                                   Tensor d_c1w, Tensor d_c1b, Tensor d_c2w, Tensor d_c2b, Tensor d_lw, Tensor d_lb, Tensor scratch) {
+    check_f32(maps, "maps", -1, maps);
+    TORCH_CHECK(n_maps >= 1 && n_maps <= INT32_MAX && map_stride >= 0 && maps.numel() >= (n_maps - 1) * map_stride + 2500,
+                "coopsearch: maps does not hold ", n_maps, " maps");
+    check_f32(c1w, "conv1.weight", 4 * 16, maps);
+    check_f32(c1b, "conv1.bias", 4, maps);
+    check_f32(c2w, "conv2.weight", 4 * 9, maps);
+    check_f32(c2b, "conv2.bias", 1, maps);
+    check_f32(lw, "linear.weight", 16 * 576, maps);
+    check_f32(lb, "linear.bias", 16, maps);
+    check_f32(dfeat, "dfeat", n_maps * 16, maps);
+    check_f32(d_c1w, "d conv1.weight", 4 * 16, maps);
+    check_f32(d_c1b, "d conv1.bias", 4, maps);
+    check_f32(d_c2w, "d conv2.weight", 4 * 9, maps);
+    check_f32(d_c2b, "d conv2.bias", 1, maps);
+    check_f32(d_lw, "d linear.weight", 16 * 576, maps);
+    check_f32(d_lb, "d linear.bias", 16, maps);
+    check_f32(scratch, "scratch", -1, maps);
+    const int rc = cs_policy_conv_features_backward(
+        c1w.data_ptr<float>(), c1b.data_ptr<float>(), c2w.data_ptr<float>(), c2b.data_ptr<float>(), lw.data_ptr<float>(),
+        lb.data_ptr<float>(), maps.data_ptr<float>(), map_stride, (int)n_maps, dfeat.data_ptr<float>(), d_c1w.data_ptr<float>(),
+        d_c1b.data_ptr<float>(), d_c2w.data_ptr<float>(), d_c2b.data_ptr<float>(), d_lw.data_ptr<float>(), d_lb.data_ptr<float>(),
+        scratch.data_ptr<float>(), scratch.numel(), stream_of(maps));
+    TORCH_CHECK(rc == CS_OK, cs_policy_last_error());
+}
+
 // FusedAgents.sync_weights: the agent network's ten torch-layout parameters -> the packed blob in place, one launch
 // (cs_policy_pack_device); a refused weight leaves `packed` as it was and is reported in `status` (int32 [4]), never here
 void policy_pack_device(const Tensor &fc1_w, const Tensor &fc1_b, const Tensor &w_ih, const Tensor &b_ih, const Tensor &w_hh,
@@ -559,6 +597,10 @@ TORCH_LIBRARY(coopsearch, m) {
           "Tensor(b!)? trace_row) -> ()", &epsilon_step);
     m.def("policy_conv_features(Tensor conv1_w, Tensor conv1_b, Tensor conv2_w, Tensor conv2_b, Tensor lin_w, Tensor lin_b, "
           "Tensor maps, int map_stride, int n_maps, Tensor(a!) feat) -> ()", &policy_conv_features);
+    m.def("policy_conv_features_backward_scratch(int n_maps) -> int", &policy_conv_features_backward_scratch);
+    m.def("policy_conv_features_backward(Tensor conv1_w, Tensor conv1_b, Tensor conv2_w, Tensor conv2_b, Tensor lin_w, Tensor lin_b, "
+          "Tensor maps, int map_stride, int n_maps, Tensor dfeat, Tensor(a!) d_conv1_w, Tensor(b!) d_conv1_b, Tensor(c!) d_conv2_w, "
+          "Tensor(d!) d_conv2_b, Tensor(e!) d_lin_w, Tensor(f!) d_lin_b, Tensor(g!) scratch) -> ()", &policy_conv_features_backward);
     m.def("policy_pack_device(Tensor fc1_w, Tensor fc1_b, Tensor w_ih, Tensor b_ih, Tensor w_hh, Tensor b_hh, Tensor fc2a_w, "
           "Tensor fc2a_b, Tensor fc2b_w, Tensor fc2b_b, Tensor(a!) packed, Tensor(b!) status) -> ()", &policy_pack_device);
     m.def("rollout_policy(Tensor cfg, Tensor(a!) state, Tensor packed, Tensor(b!) hidden, Tensor last, int T, int flags, "

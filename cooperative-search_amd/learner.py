@@ -21,6 +21,10 @@ over all rows in torch.
 Every `learn` also takes a batch in the map-once format of the flight variant (replay.COMPACT_KEYS) as
 it is.  QMIX and REINFORCE never build `o` / `o_next` from it: the conv front end runs once per (episode, step) on the map
 (`map_features`), its 16 features are broadcast over the agents, and the rest of the unroll is the one above.
+
+`conv_impl="hip"` (opt-in on every learner) takes that conv front end from `ConvFeatures` instead of the
+torch modules: the acting kernel (k_conv_features) forward, k_conv_features_bwd (csrc/conv_bwd.h) backward, so that a flight
+learn step makes no MIOpen call.  The default, "torch", is the modules.
 """
 import os
 
@@ -28,7 +32,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .agents import AgentRNN, rnn_input_shape
+from .agents import AgentRNN, FusedAgents, rnn_input_shape
 from .replay import expand_compact
 
 HIDDEN = 64   # rnn_hidden_dim: the recurrence kernels are built for it (get_mixer_args, common/arguments.py:58)
@@ -100,9 +104,99 @@ class GRUSequence(torch.autograd.Function):
         return (dgi if need_gi else None), dw, db, dh0
 
 
+CONV_IMPLS = ("torch", "hip")
+CONV_FRONT_END = FusedAgents.CONV_HYPER   # what the conv kernels are built for: the reference's flight hyper-parameters
+CONV_CELLS, CONV_FEATURES = 2500, 16
+
+
+def check_conv_impl(args, device, unroll, conv_impl):
+    """The learners' `conv_impl` argument: "torch" (the default: net.conv / net.linear, i.e. MIOpen) or "hip" (ConvFeatures: the
+    acting kernel forward, k_conv_features_bwd backward).  "hip" needs what the kernels need; every refusal names its reason."""
+    if conv_impl not in CONV_IMPLS:
+        raise ValueError(f"conv_impl must be 'torch' or 'hip', not {conv_impl!r}")
+    if conv_impl == "torch":
+        return conv_impl
+    if unroll != "fused":
+        raise ValueError("conv_impl='hip' needs unroll='fused': the reference's step loop (unroll='torch') runs the torch modules")
+    if torch.device(device).type != "cuda":
+        raise ValueError(f"conv_impl='hip' needs a GPU device: the conv kernels do not run on {torch.device(device).type!r}")
+    if not getattr(args, "conv", False):
+        raise ValueError("conv_impl='hip' needs the conv front end (args.conv): this variant's network has none")
+    other = {k: getattr(args, k, None) for k, v in CONV_FRONT_END.items() if getattr(args, k, None) != v}
+    if other:
+        raise ValueError(f"conv_impl='hip' is built for the reference's front-end hyper-parameters {CONV_FRONT_END}; "
+                         f"these differ: {other}")
+    return conv_impl
+
+
+def _conv_weights(net):
+    return (net.conv[0].weight, net.conv[0].bias, net.conv[2].weight, net.conv[2].bias, net.linear.weight, net.linear.bias)
+
+
+def _conv_forward(weights, maps, map_stride, n_maps):
+    """policy_conv_features on torch tensors -> feat [n_maps, 16] (no graph)."""
+    feat = maps.new_empty(n_maps, CONV_FEATURES)
+    _ops().policy_conv_features(*weights, maps, int(map_stride), int(n_maps), feat)
+    return feat
+
+
+_CONV_SCRATCH = {}   # (device, stream) -> the backward's partial-sum buffer, kept between calls (its contents mean nothing afterwards)
+
+
+def _conv_scratch(like, floats):
+    key = (like.device, torch.cuda.current_stream(like.device).cuda_stream)   # calls on one stream are ordered: one buffer serves them
+    buf = _CONV_SCRATCH.get(key)
+    if buf is None or buf.numel() < floats:
+        buf = _CONV_SCRATCH[key] = like.new_empty(floats)
+    return buf
+
+
+class ConvFeatures(torch.autograd.Function):
+    """(maps, map_stride, n_maps, conv1.weight, conv1.bias, conv2.weight, conv2.bias, linear.weight, linear.bias) -> feat
+    [n_maps, 16]: the conv front end of AgentRNN.forward.  maps: a contiguous float32 tensor, map m = 2500 floats at element
+    m * map_stride (a [n_maps, 2500] table, or rows that carry the map in front: map_stride = row width).  Forward is
+    policy_conv_features as it is, so learning sees the acting kernel's features bit for bit; backward is
+    policy_conv_features_backward (the six weight gradients; both activation planes recomputed from the maps, nothing but
+    the maps kept).  The maps are data: one that requires grad is refused."""
+
+    @staticmethod
+    def forward(ctx, maps, map_stride, n_maps, *weights):
+        if ctx.needs_input_grad[0]:
+            raise ValueError("ConvFeatures: no gradient with respect to the maps (they are data); detach them")
+        weights = tuple(w.detach().contiguous() for w in weights)
+        maps = maps.detach()
+        feat = _conv_forward(weights, maps, map_stride, n_maps)
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(maps, *weights)
+            ctx.geometry = (int(map_stride), int(n_maps))
+        return feat
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        maps, *weights = ctx.saved_tensors
+        map_stride, n_maps = ctx.geometry
+        ops = _ops()
+        grads = [torch.empty_like(w) for w in weights]
+        scratch = _conv_scratch(maps, int(ops.policy_conv_features_backward_scratch(n_maps)))
+        ops.policy_conv_features_backward(*weights, maps, map_stride, n_maps, dfeat.contiguous(), *grads, scratch)
+        return (None, None, None, *[g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])])
+
+
+def _conv_features(net, maps, map_stride, n_maps):
+    """net's front end on the conv kernels: with a graph (ConvFeatures) when gradients are on, else the forward op alone."""
+    weights = _conv_weights(net)
+    if torch.is_grad_enabled():
+        return ConvFeatures.apply(maps, int(map_stride), int(n_maps), *weights)
+    return _conv_forward(tuple(w.detach().contiguous() for w in weights), maps, map_stride, n_maps)
+
+
 def map_features(net, maps):
-    """The conv front end of AgentRNN.forward on maps [..., cells] -> [..., conv_out_dim]: the same modules, one row per map."""
+    """The conv front end of AgentRNN.forward on maps [..., cells] -> [..., conv_out_dim]: the same modules, one row per map
+    (net.conv_impl == "hip", set by the learners: the conv kernels on the same weights)."""
     a = net.args
+    if getattr(net, "conv_impl", "torch") == "hip":
+        flat = maps.detach().reshape(-1, CONV_CELLS).contiguous()
+        return _conv_features(net, flat, CONV_CELLS, flat.shape[0]).view(*maps.shape[:-1], -1)
     prob = maps.reshape(-1, 1, a.map_size, a.map_size)
     feat = net.linear(net.conv(prob).reshape(-1, a.dim_2 * net.conv_size ** 2))
     return feat.view(*maps.shape[:-1], -1)
@@ -133,8 +227,12 @@ def unroll_q(net, X, h0=None, impl="fused", featured=False):
     x = X.reshape(T * R, -1)
     if net.args.conv and not featured:   # the same modules on the same maps as AgentRNN.forward, all T*R maps in one call
         cells = net.args.map_size ** 2
-        prob = x[:, :cells].reshape(-1, 1, net.args.map_size, net.args.map_size)
-        feat = net.linear(net.conv(prob).reshape(-1, net.args.dim_2 * net.conv_size ** 2))
+        if getattr(net, "conv_impl", "torch") == "hip":   # the maps where they lie, in front of every row: no copy
+            x = x.contiguous()
+            feat = _conv_features(net, x.detach(), x.shape[1], T * R)
+        else:
+            prob = x[:, :cells].reshape(-1, 1, net.args.map_size, net.args.map_size)
+            feat = net.linear(net.conv(prob).reshape(-1, net.args.dim_2 * net.conv_size ** 2))
         x = torch.cat([feat, x[:, cells:]], 1)
     x = F.relu(net.fc1(x))
     gi = F.linear(x, net.rnn.weight_ih, net.rnn.bias_ih).view(T, R, 3 * HIDDEN)
@@ -260,11 +358,13 @@ def with_narrow_keys(batch, n_agents, n_actions):
 class QMixLearner:
     """policy/qmix.py:QMIX on the device.  args: the reference's namespace after get_mixer_args (seed, lr, optimizer, gamma,
     tau, grad_norm_clip, qmix_hidden_dim, two_hyper_layers, hyper_hidden_dim, rnn_hidden_dim) and the env fields
-    (apply_env_info).  unroll: "fused" (GRUSequence, needs the HIP library and a GPU) or "torch" (the reference's loop)."""
+    (apply_env_info).  unroll: "fused" (GRUSequence, needs the HIP library and a GPU) or "torch" (the reference's loop).
+    conv_impl (flight's conv front end in `learn`): "torch" (the modules) or "hip" (ConvFeatures; check_conv_impl)."""
 
-    def __init__(self, args, device="cuda", unroll="fused"):
+    def __init__(self, args, device="cuda", unroll="fused", conv_impl="torch"):
         if unroll not in ("fused", "torch"):
             raise ValueError("unroll must be 'fused' or 'torch'")
+        self.conv_impl = check_conv_impl(args, device, unroll, conv_impl)
         self.args, self.device, self.unroll = args, torch.device(device), unroll
         self.n_actions, self.n_agents = args.n_actions, args.n_agents
         self.state_shape, self.obs_shape = args.state_shape, args.obs_shape
@@ -278,6 +378,7 @@ class QMixLearner:
         self.target_qmix_net = MixerNet(args)
         for net in (self.eval_rnn, self.target_rnn, self.eval_qmix_net, self.target_qmix_net):
             net.to(self.device)
+        self.eval_rnn.conv_impl = self.target_rnn.conv_impl = self.conv_impl   # read by map_features / unroll_q
         self.model_dir = model_dir(args, "qmix")
         self.target_rnn.load_state_dict(self.eval_rnn.state_dict())
         self.target_qmix_net.load_state_dict(self.eval_qmix_net.state_dict())
@@ -517,11 +618,13 @@ class DOPLearner:
     optimizer, gamma, tau, grad_norm_clip, offpg_hidden_dim, qmix_hidden_dim, two_hyper_layers, hyper_hidden_dim,
     rnn_hidden_dim) and the env fields (apply_env_info).  unroll: "fused" (the critic over all T*E*n rows at once, the actor
     through GRUSequence, the TD(lambda) target from cs_episode_returns; needs the HIP library and a GPU) or "torch" (the
-    reference's per-transition loops and its O(T^2) lambda-return, over the same modules; also runs on the CPU)."""
+    reference's per-transition loops and its O(T^2) lambda-return, over the same modules; also runs on the CPU).
+    conv_impl: the ACTOR's conv front end, as QMixLearner's (the critic reads the raw map through its own linear layer)."""
 
-    def __init__(self, args, device="cuda", unroll="fused"):
+    def __init__(self, args, device="cuda", unroll="fused", conv_impl="torch"):
         if unroll not in ("fused", "torch"):
             raise ValueError("unroll must be 'fused' or 'torch'")
+        self.conv_impl = check_conv_impl(args, device, unroll, conv_impl)
         self.args, self.device, self.unroll = args, torch.device(device), unroll
         self.n_actions, self.n_agents = args.n_actions, args.n_agents
         self.state_shape, self.obs_shape = args.state_shape, args.obs_shape
@@ -539,6 +642,7 @@ class DOPLearner:
         self.target_mixer_net = MixerNet(args)
         for net in (self.actor, self.eval_critic, self.target_critic, self.eval_mixer_net, self.target_mixer_net):
             net.to(self.device)
+        self.actor.conv_impl = self.conv_impl   # read by map_features / unroll_q
         self.model_dir = model_dir(args, "dop")
         self.target_critic.load_state_dict(self.eval_critic.state_dict())
         self.target_mixer_net.load_state_dict(self.eval_mixer_net.state_dict())
@@ -650,16 +754,18 @@ class ReinforceLearner:
     """policy/reinforce.py:Reinforce on the device.  args: the reference's namespace after get_reinforce_args (seed, lr_actor,
     optimizer, gamma, rnn_hidden_dim) and the env fields.  On-policy: `learn` takes the episode dict that
     EpisodeCollector.generate_episodes returns (or a sampled batch).  unroll: "fused" (GRUSequence and cs_episode_returns) or
-    "torch" (the reference's step loops)."""
+    "torch" (the reference's step loops).  conv_impl: as QMixLearner's."""
 
-    def __init__(self, args, device="cuda", unroll="fused"):
+    def __init__(self, args, device="cuda", unroll="fused", conv_impl="torch"):
         if unroll not in ("fused", "torch"):
             raise ValueError("unroll must be 'fused' or 'torch'")
+        self.conv_impl = check_conv_impl(args, device, unroll, conv_impl)
         self.args, self.device, self.unroll = args, torch.device(device), unroll
         self.n_actions, self.n_agents = args.n_actions, args.n_agents
         self.state_shape, self.obs_shape = args.state_shape, args.obs_shape
         torch.manual_seed(args.seed)   # reinforce.py:22-31
         self.eval_rnn = AgentRNN(rnn_input_shape(args), args).to(self.device)
+        self.eval_rnn.conv_impl = self.conv_impl   # read by map_features / unroll_q
         self.model_dir = model_dir(args, "reinforce")
         self.rnn_parameters = list(self.eval_rnn.parameters())
         self.rnn_optimizer = _make_optimizer(args, self.rnn_parameters, args.lr_actor)

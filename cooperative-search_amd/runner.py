@@ -65,7 +65,7 @@ class Runner:
     get_reinforce_args and apply_env_info; args.alg selects the learner.  The parts (learner, agents, schedule, collector,
     buffer) are built here unless passed in.  args.compact_episodes (flight only; default False): episodes are collected,
     stored and learnt from in the map-once format (replay.COMPACT_KEYS) -- a CompactReplayBuffer and
-    generate_episodes(compact=True); the schedule of calls is the same."""
+    generate_episodes(compact=True); the schedule of calls is the same.  args.conv_impl (absent: "torch") goes to the learner."""
 
     def __init__(self, env, args, learner=None, agents=None, schedule=None, collector=None, buffer=None):
         alg = getattr(args, "alg", None)
@@ -75,7 +75,9 @@ class Runner:
             raise ValueError(f"Runner: no such algorithm {alg!r} (qmix, dop or reinforce)")
         self.env, self.args = env, apply_run_defaults(args)
         device = getattr(env, "device", "cuda")
-        self.learner = learner if learner is not None else LEARNERS[alg](args, device)
+        if learner is None:   # args.conv_impl (absent: "torch"): the learners' conv front end, learner.check_conv_impl
+            learner = LEARNERS[alg](args, device, conv_impl=getattr(args, "conv_impl", "torch"))
+        self.learner = learner
         self.model_path = args.model_dir + run_name(args)
         if args.load_model:   # policy/*.py __init__: the newest checkpoint of the learner's own directory
             idx = get_model_idx(self.model_path) - 1

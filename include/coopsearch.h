@@ -316,6 +316,21 @@ int cs_epsilon_step(const cs_config *cfg, void *state_dev, int flags, double *ep
 int cs_policy_conv_features(const float *conv1_w_dev, const float *conv1_b_dev, const float *conv2_w_dev,
                             const float *conv2_b_dev, const float *lin_w_dev, const float *lin_b_dev,
                             const float *maps_dev, int64_t map_stride, int n_maps, float *feat_dev, void *stream);
+/* The backward pass of cs_policy_conv_features for the learners: dfeat_dev [n_maps][16] = dloss/dfeat of every map -> the
+ * six weight gradients in the weights' own layouts (64, 4, 36, 1, 16*576 and 16 floats), summed over all maps and WRITTEN
+ * (not accumulated).  No gradient with respect to the maps.  Nothing is kept from the forward: both activation planes are
+ * recomputed on chip with the forward's own arithmetic, so the ReLU gates are exactly the ones the forward applied.  A map
+ * whose 16 dfeat values are all zero is skipped.  No float atomics: every workgroup writes one partial gradient set to
+ * scratch_dev and a second launch adds the sets in a fixed order, so reruns are bit-identical.  scratch_dev holds at least
+ * the number of floats that cs_policy_conv_features_backward_scratch(n_maps, &floats) reports (a function of the device and
+ * n_maps only); its contents need not be initialised and mean nothing afterwards. */
+int cs_policy_conv_features_backward_scratch(int n_maps, int64_t *floats_out);
+int cs_policy_conv_features_backward(const float *conv1_w_dev, const float *conv1_b_dev, const float *conv2_w_dev,
+                                     const float *conv2_b_dev, const float *lin_w_dev, const float *lin_b_dev,
+                                     const float *maps_dev, int64_t map_stride, int n_maps, const float *dfeat_dev,
+                                     float *d_conv1_w_dev, float *d_conv1_b_dev, float *d_conv2_w_dev, float *d_conv2_b_dev,
+                                     float *d_lin_w_dev, float *d_lin_b_dev, float *scratch_dev, int64_t scratch_floats,
+                                     void *stream);
 const char *cs_policy_last_error(void);
 
 /* Fused closed loop (flight_easy, n_agents <= 5): T x (cs_policy_forward -> cs_step) in ONE launch, i.e. the body of
