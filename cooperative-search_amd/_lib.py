@@ -1,7 +1,10 @@
-"""ctypes binding of libcoopsearch_hip.so (include/coopsearch.h).  No fallback: a missing library raises."""
+"""ctypes binding of libcoopsearch_hip.so (include/coopsearch.h) and the choice between it and torch.ops.coopsearch
+(`pick_binding`: either way the package calls one ops object).  No fallback: a missing library raises."""
 import ctypes as C
 import os
 import warnings
+
+import torch
 
 from . import build as _build
 
@@ -169,7 +172,6 @@ def torch_ops():
     global _ops
     if _ops is not None:
         return _ops
-    import torch
     load()   # libcoopsearch_hip.so first: coopsearch_torch.so links it
     if _build.torch_ops_stale():
         if _build.cxx_path() is None:
@@ -186,14 +188,163 @@ def torch_ops():
     return _ops
 
 
+def _cfg(cfg):
+    """The cs_config whose bytes the CPU uint8 tensor `cfg` holds (what the ops take; BatchedFlightEnv._cfg_t), in place."""
+    return CsConfig.from_address(cfg.data_ptr())
+
+
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+def _epsilon(epsilon, eps_env, anneal, min_epsilon, per_step, eps_trace):
+    return CsEpsilon(epsilon, anneal, min_epsilon, 1 if per_step else 0, 0, _p(eps_env), _p(eps_trace))
+
+
+def _action_flags(cfg, actions, flags):
+    """action_flags of csrc/torch_ops.cpp: ACTIONS_I64 from the dtype; CHECK_ACTIONS as the caller decided (CHECK_ACTIONS = on,
+    OP_NO_CHECK_ACTIONS = off, a bit that never reaches the C ABI), else check_actions_default(batch)."""
+    if flags & (CHECK_ACTIONS | OP_NO_CHECK_ACTIONS):
+        on = not flags & OP_NO_CHECK_ACTIONS
+    else:
+        on = check_actions_default(_cfg(cfg).batch)
+    return (flags & ~(ACTIONS_I64 | CHECK_ACTIONS | OP_NO_CHECK_ACTIONS)) | (ACTIONS_I64 if actions.dtype == torch.int64 else 0) \
+        | (CHECK_ACTIONS if on else 0)
+
+
+class CtypesOps:
+    """The ctypes twin of torch.ops.coopsearch: the ops the package calls, under the same names and with the same arguments
+    (tests/test_capi_cpu.py holds the two together), straight to the C ABI.  A method makes its tensors' device current, takes
+    torch's current stream on it, turns tensors into pointers and raises from the entry point's `*_last_error`; it checks no
+    tensor -- the op layer's TORCH_CHECKs have no counterpart here."""
+
+    def __init__(self):
+        self._L = load()
+
+    def _launch(self, on, fn, *args, error=None):
+        """fn(*args, stream): the cs_* entry points launch on the process's current device, so `on`'s device is made current
+        for the call (the ops do the same in C++ with a HIPGuard); an env on cuda:1 works while cuda:0 is current."""
+        with torch.cuda.device(on.device):
+            rc = fn(*args, torch.cuda.current_stream(on.device).cuda_stream)
+        if error is None:
+            check(rc)
+        elif rc != 0:
+            raise CoopSearchError(error().decode())
+
+    def _env(self, fn, cfg, state, *args):
+        self._launch(state, fn, _cfg(cfg), state.data_ptr(), *args)
+
+    def _policy(self, on, fn, *args):
+        self._launch(on, fn, *args, error=self._L.cs_policy_last_error)
+
+    def state_bytes(self, cfg):
+        lay = CsLayout()
+        check(self._L.cs_state_layout(_cfg(cfg), C.byref(lay)))
+        return lay.total_bytes
+
+    def env_init(self, cfg, state):
+        self._env(self._L.cs_init, cfg, state)
+
+    def env_seed(self, cfg, state, seeds):
+        self._env(self._L.cs_seed, cfg, state, _p(seeds))
+
+    def env_reset(self, cfg, state, mask, init, obs, state_out):
+        self._env(self._L.cs_reset, cfg, state, _p(mask), 1 if init else 0, _p(obs), _p(state_out))
+
+    def env_step(self, cfg, state, actions, flags, reward, terminated, win, obs, state_out):
+        self._env(self._L.cs_step, cfg, state, _p(actions), _action_flags(cfg, actions, flags), _p(reward), _p(terminated), _p(win),
+                  _p(obs), _p(state_out))
+
+    def env_rollout(self, cfg, state, actions, flags, reward, terminated, win, obs, state_out):
+        self._env(self._L.cs_rollout, cfg, state, _p(actions), actions.shape[0], _action_flags(cfg, actions, flags), _p(reward),
+                  _p(terminated), _p(win), _p(obs), _p(state_out))
+
+    def env_emit(self, cfg, state, obs, state_out):
+        self._env(self._L.cs_emit, cfg, state, _p(obs), _p(state_out))
+
+    def env_metrics(self, cfg, state, out4):
+        self._env(self._L.cs_metrics, cfg, state, _p(out4))
+
+    def mt_advance(self, cfg, state, min_ahead):
+        self._env(self._L.cs_mt_advance, cfg, state, min_ahead)
+
+    def mt_canonical(self, cfg, state, rows_out):
+        self._env(self._L.cs_mt_canonical, cfg, state, _p(rows_out))
+
+    def epsilon_step(self, cfg, state, flags, eps_env, anneal, min_epsilon, trace_row):
+        self._env(self._L.cs_epsilon_step, cfg, state, flags, _p(eps_env), anneal, min_epsilon, _p(trace_row))
+
+    def policy_forward(self, packed, obs, obs_stride, obs_offset, last, feat, rows_per_feat, hidden, q, actions, rows, n_agents,
+                       n_actions, epsilon, eps_env, seed, step, row0, select):
+        self._policy(packed, self._L.cs_policy_forward, _p(packed), _p(obs), obs_stride, obs_offset, _p(last), _p(feat),
+                     rows_per_feat, _p(hidden), _p(q), _p(actions), rows, n_agents, n_actions, epsilon, _p(eps_env), seed, step, row0,
+                     select)
+
+    def policy_conv_features(self, conv1_w, conv1_b, conv2_w, conv2_b, lin_w, lin_b, maps, map_stride, n_maps, feat):
+        self._policy(maps, self._L.cs_policy_conv_features, _p(conv1_w), _p(conv1_b), _p(conv2_w), _p(conv2_b), _p(lin_w), _p(lin_b),
+                     _p(maps), map_stride, n_maps, _p(feat))
+
+    def policy_pack_device(self, fc1_w, fc1_b, w_ih, b_ih, w_hh, b_hh, fc2a_w, fc2a_b, fc2b_w, fc2b_b, packed, status):
+        ws = (fc1_w, fc1_b, w_ih, b_ih, w_hh, b_hh, fc2a_w, fc2a_b, fc2b_w, fc2b_b)
+        self._policy(packed, self._L.cs_policy_pack_device, *map(_p, ws), fc1_w.shape[1], fc2b_w.shape[0], _p(packed), _p(status))
+
+    def _closed_loop(self, fn, cfg, state, ins, T, flags, eps, seed, step0, row0, select, outs):
+        self._env(fn, cfg, state, *map(_p, ins), T, flags, C.byref(eps), seed, step0, row0, select, *map(_p, outs))
+
+    def rollout_policy(self, cfg, state, packed, hidden, last, T, flags, epsilon, eps_env, anneal, min_epsilon, per_step, eps_trace,
+                       seed, step0, row0, select, actions, reward, terminated, win, obs, state_out):
+        self._closed_loop(self._L.cs_rollout_policy, cfg, state, (packed, hidden, last), T, flags,
+                          _epsilon(epsilon, eps_env, anneal, min_epsilon, per_step, eps_trace), seed, step0, row0, select,
+                          (actions, reward, terminated, win, obs, state_out))
+
+    def rollout_policy_flight(self, cfg, state, packed, c1w, c1b, c2w, c2b, lw, lb, hidden, last, scratch, T, flags, epsilon, eps_env,
+                              anneal, min_epsilon, per_step, eps_trace, seed, step0, row0, select, actions, reward, terminated, win,
+                              obs, state_out):
+        self._closed_loop(self._L.cs_rollout_policy_flight, cfg, state, (packed, c1w, c1b, c2w, c2b, lw, lb, hidden, last, scratch),
+                          T, flags, _epsilon(epsilon, eps_env, anneal, min_epsilon, per_step, eps_trace), seed, step0, row0, select,
+                          (actions, reward, terminated, win, obs, state_out))
+
+    def collect_flight(self, cfg, state, packed, c1w, c1b, c2w, c2b, lw, lb, hidden, last, scratch, T, flags, epsilon, eps_env,
+                       anneal, min_epsilon, per_step, eps_trace, seed, step0, row0, select, actions, reward, terminated, win,
+                       map_tab, state_tab):
+        self._closed_loop(self._L.cs_collect_flight, cfg, state, (packed, c1w, c1b, c2w, c2b, lw, lb, hidden, last, scratch),
+                          T, flags, _epsilon(epsilon, eps_env, anneal, min_epsilon, per_step, eps_trace), seed, step0, row0, select,
+                          (actions, reward, terminated, win, map_tab, state_tab))
+
+    def store_episodes(self, o_tab, s_tab, u_tab, r_tab, term_tab, slots, n_actions, outs):
+        T, B, n = u_tab.shape
+        eo = CsEpisodeOut(*map(_p, outs))
+        self._launch(o_tab, self._L.cs_store_episodes, B, T, n, n_actions, o_tab.shape[-1], s_tab.shape[-1], _p(o_tab), _p(s_tab),
+                     _p(u_tab), _p(r_tab), _p(term_tab), _p(slots), C.byref(eo), error=self._L.cs_episodes_last_error)
+
+    def store_episodes_compact(self, map_tab, s_tab, u_tab, r_tab, term_tab, slots, outs):
+        T, B, n = u_tab.shape
+        if any(t.shape[1] != (T + 1 if k < 2 else T) for k, t in enumerate(outs)):   # map and s_full come first (CsCompactOut)
+            raise ValueError("assemble_episodes_compact: destinations must be [slots, T (+ 1), ...]")
+        co = CsCompactOut(*map(_p, outs))
+        self._launch(map_tab, self._L.cs_store_episodes_compact, B, T, n, map_tab.shape[-1], s_tab.shape[-1], _p(map_tab),
+                     _p(s_tab), _p(u_tab), _p(r_tab), _p(term_tab), _p(slots), C.byref(co), error=self._L.cs_episodes_last_error)
+
+
+_ctypes_ops = None
+
+
+def ctypes_ops():
+    global _ctypes_ops
+    if _ctypes_ops is None:
+        _ctypes_ops = CtypesOps()
+    return _ctypes_ops
+
+
 def pick_binding(binding=None):
-    """'torch' | 'ctypes' | None -> (name, torch.ops.coopsearch or None).  None = the torch op layer when it can be built /
-    loaded, else the ctypes route with a warning (same library, same kernels); an experimental library (COOPSEARCH_LIB) is
-    only reachable through ctypes.  An explicit 'torch' raises when the op library is unavailable."""
+    """'torch' | 'ctypes' | None -> (name, ops): torch.ops.coopsearch or its ctypes twin (`CtypesOps`), never None.  None = the
+    torch op layer when it can be built / loaded, else the ctypes route with a warning (same library, same kernels); an
+    experimental library (COOPSEARCH_LIB) is only reachable through ctypes.  An explicit 'torch' raises when the op library is
+    unavailable."""
     if binding not in (None, "torch", "ctypes"):
         raise ValueError("binding must be 'torch' (torch.ops.coopsearch, csrc/torch_ops.cpp) or 'ctypes'")
     if binding == "ctypes" or (binding is None and os.environ.get("COOPSEARCH_LIB")):
-        return "ctypes", None
+        return "ctypes", ctypes_ops()
     try:
         return "torch", torch_ops()
     except Exception as exc:   # noqa: BLE001 -- compiler missing, torch headers missing, dlopen failure, ABI mismatch
@@ -201,7 +352,7 @@ def pick_binding(binding=None):
             raise
         warnings.warn(f"torch.ops.coopsearch is unavailable ({type(exc).__name__}: {exc}); using the ctypes binding of the "
                       "same library", RuntimeWarning, stacklevel=3)
-        return "ctypes", None
+        return "ctypes", ctypes_ops()
 
 
 def has_legacy_kernels():

@@ -129,7 +129,7 @@ class FusedAgents:
             raise ValueError("FusedAgents: rnn_hidden_dim must be 64, obs_shape 4 and 4 + n_actions + n_agents <= 16")
         self._C, self._lib = C, _lib
         self._L = _lib.load()
-        # torch.ops.coopsearch.* (checks in C++, torch's stream) unless an experimental library is selected
+        # torch.ops.coopsearch.* (checks in C++, torch's stream); its ctypes twin when an experimental library is selected
         self._ops = _lib.pick_binding(None)[1]
         self.args, self.batch, self.device = args, int(batch), torch.device(device)
         self.n_agents, self.n_actions, self.cells = args.n_agents, args.n_actions, cells
@@ -178,13 +178,7 @@ class FusedAgents:
         network keeps acting, as when load_weights() raises -- and check_weights() reports it."""
         sd = self.net.state_dict()
         ws = [sd[k].detach().to(self.device, torch.float32).contiguous() for k in self.PACK_ORDER]
-        if self._ops is not None:
-            self._ops.policy_pack_device(*ws, self.packed, self.pack_status)
-        else:
-            vp = lambda t: self._C.c_void_p(t.data_ptr())
-            with self._on_device():
-                self._check(self._L.cs_policy_pack_device(*[vp(w) for w in ws], ws[0].shape[1], self.n_actions, vp(self.packed),
-                                                          vp(self.pack_status), self._stream()))
+        self._ops.policy_pack_device(*ws, self.packed, self.pack_status)
         if self.conv:
             for dst, k in zip(self.conv_w, self.CONV_KEYS):
                 dst.copy_(sd[k].detach())
@@ -201,25 +195,8 @@ class FusedAgents:
         raise self._lib.CoopSearchError(f"cs_policy_pack: {self.PACK_WEIGHTS[t]}[{i}] = {txt} is outside the fp16 range (+-65504) "
                                         "of the split-fp16 matrix path")
 
-    def _stream(self):
-        return self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _check(self, rc):
-        if rc != 0:
-            raise self._lib.CoopSearchError(self._L.cs_policy_last_error().decode())
-
-    def _on_device(self):
-        """ctypes route: the launches go to the process's current device, so this object's device is made current."""
-        return torch.cuda.device(self.device)
-
     def _conv_features(self, maps, map_stride, n_maps, feat):
-        if self._ops is not None:
-            self._ops.policy_conv_features(*self.conv_w, maps, int(map_stride), int(n_maps), feat)
-            return
-        vp = lambda t: self._C.c_void_p(t.data_ptr())
-        with self._on_device():
-            self._check(self._L.cs_policy_conv_features(*[vp(w) for w in self.conv_w], vp(maps), map_stride, n_maps,
-                                                        vp(feat), self._stream()))
+        self._ops.policy_conv_features(*self.conv_w, maps, int(map_stride), int(n_maps), feat)
 
     def init_hidden(self):
         self.hidden.zero_()
@@ -241,7 +218,6 @@ class FusedAgents:
         -1 = none) and `out` (int64 [B, n] destination, e.g. row t of its action table) to avoid any copy.
         eps_env (float64 [B] device tensor): every env explores with its OWN epsilon (the per-env exploration schedule,
         collector.EpsilonSchedule) instead of the scalar; ignored when evaluating, like rollout.py:35."""
-        C = self._C
         width = self.cells + 4
         if obs.dtype != torch.float32 or obs.shape[-1] != width or obs.numel() != self.rows * width:
             raise ValueError(f"obs must be float32 [B, n, {width}]")
@@ -252,7 +228,6 @@ class FusedAgents:
         for t in (last, out):
             if t.dtype != torch.int64 or t.numel() != self.rows or not t.is_contiguous():
                 raise ValueError("last / out must be contiguous int64 [B, n]")
-        vp = lambda t: C.c_void_p(t.data_ptr())
         if self.conv:  # the map of an env's first row stands for all its rows (flight_env.py:223-230)
             self._conv_features(obs, self.n_agents * width, self.batch, self.feat)
         eps, sel = self.selection(epsilon, evaluate)
@@ -260,41 +235,23 @@ class FusedAgents:
             eps_env = None   # epsilon = 0 if evaluate (rollout.py:35)
         if eps_env is not None and (eps_env.dtype != torch.float64 or eps_env.numel() != self.batch or not eps_env.is_contiguous()):
             raise ValueError("eps_env must be a contiguous float64 [B] tensor")
-        if self._ops is not None:
-            self._ops.policy_forward(self.packed, obs, width, self.cells, last, self.feat if self.conv else None, self.n_agents,
-                                     self.hidden, self.q if want_q else None, out, self.rows, self.n_agents, self.n_actions, eps,
-                                     eps_env, self.seed, self.calls, self.row0, sel)
-            self.calls += 1
-            return out
-        with self._on_device():
-            self._check(self._L.cs_policy_forward(vp(self.packed), vp(obs), width, self.cells, vp(last),
-                                                  vp(self.feat) if self.conv else None, self.n_agents, vp(self.hidden),
-                                                  vp(self.q) if want_q else None, vp(out), self.rows, self.n_agents,
-                                                  self.n_actions, eps, vp(eps_env) if eps_env is not None else None, self.seed,
-                                                  self.calls, self.row0, sel, self._stream()))
+        self._ops.policy_forward(self.packed, obs, width, self.cells, last, self.feat if self.conv else None, self.n_agents,
+                                 self.hidden, self.q if want_q else None, out, self.rows, self.n_agents, self.n_actions, eps,
+                                 eps_env, self.seed, self.calls, self.row0, sel)
         self.calls += 1
         return out
 
     def forward_raw(self, x, want_q=True):
         """Forward on caller-assembled input rows x [rows, (map_size^2 +) 4 + n_actions + n_agents] (greedy choice; conv
         features per ROW here, since raw rows need not share maps)."""
-        C = self._C
         x = x.to(torch.float32).contiguous()
-        vp = lambda t: C.c_void_p(t.data_ptr())
         feat = None
         if self.conv:
             feat = torch.empty(self.rows, 16, device=self.device)
             self._conv_features(x, x.stride(0), self.rows, feat)
-        if self._ops is not None:
-            self._ops.policy_forward(self.packed, x, x.stride(0), self.cells, None, feat, 1, self.hidden,
-                                     self.q if want_q else None, self.actions, self.rows, self.n_agents, self.n_actions, 0.0,
-                                     None, self.seed, self.calls, self.row0, 0)
-            return self.actions
-        with self._on_device():
-            self._check(self._L.cs_policy_forward(vp(self.packed), vp(x), x.stride(0), self.cells, None,
-                                                  vp(feat) if self.conv else None, 1, vp(self.hidden),
-                                                  vp(self.q) if want_q else None, vp(self.actions), self.rows, self.n_agents,
-                                                  self.n_actions, 0.0, None, self.seed, self.calls, self.row0, 0, self._stream()))
+        self._ops.policy_forward(self.packed, x, x.stride(0), self.cells, None, feat, 1, self.hidden,
+                                 self.q if want_q else None, self.actions, self.rows, self.n_agents, self.n_actions, 0.0,
+                                 None, self.seed, self.calls, self.row0, 0)
         return self.actions
 
     def policy(self, epsilon=0.0, evaluate=True):

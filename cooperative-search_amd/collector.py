@@ -11,7 +11,6 @@ The env arithmetic stays in the HIP kernels; the episode batch itself (masking, 
 transposition) is assembled by `cs_store_episodes` (csrc/episodes.hip) in one pass, either into fresh tensors or
 straight into the ring of a `DeviceReplayBuffer`.
 """
-import ctypes as C
 import os
 
 import torch
@@ -39,18 +38,7 @@ def assemble_episodes(o, s, u, r, term, n_actions, out=None, slots=None):
             raise ValueError("assemble_episodes: tensors must be contiguous and on one device")
     if any(out[k].dtype != torch.float32 or out[k].shape[1] != T for k in KEYS) or u.dtype != torch.int64:
         raise ValueError("assemble_episodes: destinations must be float32 [slots, T, ...] and u int64")
-    ops = _lib.pick_binding(None)[1]
-    if ops is not None:   # torch.ops.coopsearch.store_episodes: checks in C++, torch's stream
-        ops.store_episodes(o, s, u, r, term.view(torch.uint8), slots, A, [out[k] for k in KEYS])
-        return out
-    L = _lib.load()
-    eo = _lib.CsEpisodeOut(**{k: out[k].data_ptr() for k in KEYS})
-    with torch.cuda.device(dev):   # the launch goes to the process's current device
-        rc = L.cs_store_episodes(B, T, n, A, w, S, o.data_ptr(), s.data_ptr(), u.data_ptr(), r.data_ptr(),
-                                 term.view(torch.uint8).data_ptr(), slots.data_ptr() if slots is not None else None,
-                                 C.byref(eo), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise _lib.CoopSearchError(L.cs_episodes_last_error().decode())
+    _lib.pick_binding(None)[1].store_episodes(o, s, u, r, term.view(torch.uint8), slots, A, [out[k] for k in KEYS])
     return out
 
 
@@ -71,20 +59,7 @@ def assemble_episodes_compact(m, s, u, r, term, out=None, slots=None):
             raise ValueError("assemble_episodes_compact: tensors must be contiguous and on one device")
     if any(out[k].dtype != torch.float32 for k in COMPACT_KEYS) or u.dtype != torch.int64:
         raise ValueError("assemble_episodes_compact: destinations must be float32 and u int64")
-    ops = _lib.pick_binding(None)[1]
-    if ops is not None:   # torch.ops.coopsearch.store_episodes_compact: checks in C++, torch's stream
-        ops.store_episodes_compact(m, s, u, r, term.view(torch.uint8), slots, [out[k] for k in COMPACT_KEYS])
-        return out
-    L = _lib.load()
-    if any(out[k].shape[1] != (T + 1 if k in ("map", "s_full") else T) for k in COMPACT_KEYS):
-        raise ValueError("assemble_episodes_compact: destinations must be [slots, T (+ 1), ...]")
-    co = _lib.CsCompactOut(**{k: out[k].data_ptr() for k in COMPACT_KEYS})
-    with torch.cuda.device(dev):   # the launch goes to the process's current device
-        rc = L.cs_store_episodes_compact(B, T, n, cells, S, m.data_ptr(), s.data_ptr(), u.data_ptr(), r.data_ptr(),
-                                         term.view(torch.uint8).data_ptr(), slots.data_ptr() if slots is not None else None,
-                                         C.byref(co), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise _lib.CoopSearchError(L.cs_episodes_last_error().decode())
+    _lib.pick_binding(None)[1].store_episodes_compact(m, s, u, r, term.view(torch.uint8), slots, [out[k] for k in COMPACT_KEYS])
     return out
 
 

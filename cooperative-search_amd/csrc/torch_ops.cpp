@@ -8,7 +8,8 @@
 // host side, cooperative-search_amd/env.py), so the struct has exactly one definition: the header.
 //
 // Registered as torch.ops.coopsearch.* (torch.ops.load_library on the in-tree coopsearch_torch.so).  The ctypes
-// binding (cooperative-search_amd/_lib.py) stays as the torch-free route to the same C ABI.
+// binding (cooperative-search_amd/_lib.py: CtypesOps, the same ops by name and argument) stays as the check-free route to
+// the same C ABI.
 #include <ATen/hip/HIPContext.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <c10/hip/HIPStream.h>
@@ -213,6 +214,17 @@ void check_f32(const Tensor &t, const char *name, int64_t numel, const Tensor &l
     TORCH_CHECK(numel < 0 || t.numel() == numel, "coopsearch: ", name, " must have ", numel, " elements, got ", t.numel());
 }
 
+// the six tensors of flight's conv front end (network/base_net.py:9-18), torch layout
+void check_conv_weights(const Tensor &c1w, const Tensor &c1b, const Tensor &c2w, const Tensor &c2b, const Tensor &lw, const Tensor &lb,
+                        const Tensor &like) {
+    check_f32(c1w, "conv1.weight", 4 * 16, like);
+    check_f32(c1b, "conv1.bias", 4, like);
+    check_f32(c2w, "conv2.weight", 4 * 9, like);
+    check_f32(c2b, "conv2.bias", 1, like);
+    check_f32(lw, "linear.weight", 16 * 576, like);
+    check_f32(lb, "linear.bias", 16, like);
+}
+
 int64_t policy_packed_floats() { return (int64_t)cs_policy_packed_floats(); }
 
 // Agents.choose_action (agent/agent.py:33-97) for rows = B * n_agents rows in one launch (cs_policy_forward)
@@ -249,12 +261,7 @@ void policy_conv_features(const Tensor &c1w, const Tensor &c1b, const Tensor &c2
                           const Tensor &lb, const Tensor &maps, int64_t map_stride, int64_t n_maps, Tensor feat) {
     check_f32(maps, "maps", -1, maps);
     TORCH_CHECK(n_maps >= 1 && maps.numel() >= (n_maps - 1) * map_stride + 2500, "coopsearch: maps does not hold ", n_maps, " maps");
-    check_f32(c1w, "conv1.weight", 4 * 16, maps);
-    check_f32(c1b, "conv1.bias", 4, maps);
-    check_f32(c2w, "conv2.weight", 4 * 9, maps);
-    check_f32(c2b, "conv2.bias", 1, maps);
-    check_f32(lw, "linear.weight", 16 * 576, maps);
-    check_f32(lb, "linear.bias", 16, maps);
+    check_conv_weights(c1w, c1b, c2w, c2b, lw, lb, maps);
     check_f32(feat, "feat", n_maps * 16, maps);
     const int rc = cs_policy_conv_features(c1w.data_ptr<float>(), c1b.data_ptr<float>(), c2w.data_ptr<float>(), c2b.data_ptr<float>(),
                                            lw.data_ptr<float>(), lb.data_ptr<float>(), maps.data_ptr<float>(), map_stride, (int)n_maps,
@@ -278,12 +285,7 @@ void policy_conv_features_backward(const Tensor &c1w, const Tensor &c1b, const T
     check_f32(maps, "maps", -1, maps);
     TORCH_CHECK(n_maps >= 1 && n_maps <= INT32_MAX && map_stride >= 0 && maps.numel() >= (n_maps - 1) * map_stride + 2500,
                 "coopsearch: maps does not hold ", n_maps, " maps");
-    check_f32(c1w, "conv1.weight", 4 * 16, maps);
-    check_f32(c1b, "conv1.bias", 4, maps);
-    check_f32(c2w, "conv2.weight", 4 * 9, maps);
-    check_f32(c2b, "conv2.bias", 1, maps);
-    check_f32(lw, "linear.weight", 16 * 576, maps);
-    check_f32(lb, "linear.bias", 16, maps);
+    check_conv_weights(c1w, c1b, c2w, c2b, lw, lb, maps);
     check_f32(dfeat, "dfeat", n_maps * 16, maps);
     check_f32(d_c1w, "d conv1.weight", 4 * 16, maps);
     check_f32(d_c1b, "d conv1.bias", 4, maps);
@@ -358,12 +360,9 @@ void epsilon_step(const Tensor &cfg, const Tensor &state, int64_t flags, Tensor 
                        stream_of(state)));
 }
 
-// T x (cs_policy_forward -> cs_step) in one launch (cs_rollout_policy; flight_easy, n_agents <= 5)
-void rollout_policy(const Tensor &cfg, Tensor state, const Tensor &packed, Tensor hidden, const Tensor &last, int64_t T, int64_t flags,
-                    double epsilon, c10::optional<Tensor> eps_env, double anneal, double min_epsilon, bool per_step,
-                    c10::optional<Tensor> eps_trace, int64_t seed, int64_t step0, int64_t row0, int64_t select, Tensor actions,
-                    Tensor reward, Tensor terminated, Tensor win, c10::optional<Tensor> obs, c10::optional<Tensor> state_out) {
-    const cs_config &c = config_of(cfg);
+// what every closed loop (T x policy forward -> env step in one call) takes: the network, its recurrent state, the step tables
+void check_closed_loop(const cs_config &c, const Tensor &state, int64_t T, const Tensor &packed, const Tensor &hidden,
+                       const Tensor &last, const Tensor &actions, const Tensor &reward, const Tensor &terminated, const Tensor &win) {
     check_state(c, state);
     const Shapes s = shapes_of(c);
     TORCH_CHECK(T >= 1, "coopsearch: T must be >= 1");
@@ -374,12 +373,40 @@ void rollout_policy(const Tensor &cfg, Tensor state, const Tensor &packed, Tenso
     check_dev(reward, "reward", at::kFloat, T * s.B, state);
     check_dev(terminated, "terminated", at::kByte, T * s.B, state);
     check_dev(win, "win", at::kByte, T * s.B, state);
+}
+
+// T x (cs_policy_forward -> cs_step) in one launch (cs_rollout_policy; flight_easy, n_agents <= 5)
+void rollout_policy(const Tensor &cfg, Tensor state, const Tensor &packed, Tensor hidden, const Tensor &last, int64_t T, int64_t flags,
+                    double epsilon, c10::optional<Tensor> eps_env, double anneal, double min_epsilon, bool per_step,
+                    c10::optional<Tensor> eps_trace, int64_t seed, int64_t step0, int64_t row0, int64_t select, Tensor actions,
+                    Tensor reward, Tensor terminated, Tensor win, c10::optional<Tensor> obs, c10::optional<Tensor> state_out) {
+    const cs_config &c = config_of(cfg);
+    check_closed_loop(c, state, T, packed, hidden, last, actions, reward, terminated, win);
     check_outputs(c, state, T, obs, state_out);
-    const cs_epsilon sched = schedule_of(epsilon, eps_env, anneal, min_epsilon, per_step, eps_trace, T, s.B, state);
+    const cs_epsilon sched = schedule_of(epsilon, eps_env, anneal, min_epsilon, per_step, eps_trace, T, c.batch, state);
     ok(cs_rollout_policy(&c, state.data_ptr(), packed.data_ptr<float>(), hidden.data_ptr<float>(), last.data_ptr<int64_t>(), (int)T,
                          (int)flags, &sched, (uint64_t)seed, (uint32_t)step0, (uint64_t)row0, (int)select,
                          actions.data_ptr<int64_t>(), reward.data_ptr<float>(), terminated.data_ptr<uint8_t>(),
                          win.data_ptr<uint8_t>(), opt_ptr<float>(obs), opt_ptr<float>(state_out), stream_of(state)));
+}
+
+// flight's closed loop: cs_rollout_policy_flight and cs_collect_flight take the same arguments but for their last two tables
+// (tab_a / tab_b: obs / state_out, NULL allowed, or map_tab / state_tab), which the two ops below check before they come here
+void flight_closed_loop(decltype(&cs_rollout_policy_flight) fn, const cs_config &c, Tensor &state, const Tensor &packed,
+                        const Tensor &c1w, const Tensor &c1b, const Tensor &c2w, const Tensor &c2b, const Tensor &lw, const Tensor &lb,
+                        Tensor &hidden, const Tensor &last, Tensor &scratch, int64_t T, int64_t flags, double epsilon,
+                        c10::optional<Tensor> &eps_env, double anneal, double min_epsilon, bool per_step,
+                        c10::optional<Tensor> &eps_trace, int64_t seed, int64_t step0, int64_t row0, int64_t select, Tensor &actions,
+                        Tensor &reward, Tensor &terminated, Tensor &win, float *tab_a, float *tab_b) {
+    check_closed_loop(c, state, T, packed, hidden, last, actions, reward, terminated, win);
+    check_conv_weights(c1w, c1b, c2w, c2b, lw, lb, state);
+    check_f32(scratch, "scratch", c.batch * (16 + 4 * (int64_t)c.n_agents), state);
+    const cs_epsilon sched = schedule_of(epsilon, eps_env, anneal, min_epsilon, per_step, eps_trace, T, c.batch, state);
+    ok(fn(&c, state.data_ptr(), packed.data_ptr<float>(), c1w.data_ptr<float>(), c1b.data_ptr<float>(), c2w.data_ptr<float>(),
+          c2b.data_ptr<float>(), lw.data_ptr<float>(), lb.data_ptr<float>(), hidden.data_ptr<float>(), last.data_ptr<int64_t>(),
+          scratch.data_ptr<float>(), (int)T, (int)flags, &sched, (uint64_t)seed, (uint32_t)step0, (uint64_t)row0, (int)select,
+          actions.data_ptr<int64_t>(), reward.data_ptr<float>(), terminated.data_ptr<uint8_t>(), win.data_ptr<uint8_t>(), tab_a, tab_b,
+          stream_of(state)));
 }
 
 // flight: T x (conv features of the env's map -> policy forward -> env step) enqueued by one call (cs_rollout_policy_flight)
@@ -391,30 +418,10 @@ void rollout_policy_flight(const Tensor &cfg, Tensor state, const Tensor &packed
                            c10::optional<Tensor> obs, c10::optional<Tensor> state_out) {
     const cs_config &c = config_of(cfg);
     check_state(c, state);
-    const Shapes s = shapes_of(c);
-    TORCH_CHECK(T >= 1, "coopsearch: T must be >= 1");
-    check_f32(packed, "packed", (int64_t)cs_policy_packed_floats(), state);
-    check_f32(c1w, "conv1.weight", 4 * 16, state);
-    check_f32(c1b, "conv1.bias", 4, state);
-    check_f32(c2w, "conv2.weight", 4 * 9, state);
-    check_f32(c2b, "conv2.bias", 1, state);
-    check_f32(lw, "linear.weight", 16 * 576, state);
-    check_f32(lb, "linear.bias", 16, state);
-    check_f32(hidden, "hidden", s.B * s.n * 64, state);
-    check_dev(last, "last", at::kLong, s.B * s.n, state);
-    check_f32(scratch, "scratch", s.B * (16 + 4 * s.n), state);
-    check_dev(actions, "actions", at::kLong, T * s.B * s.n, state);
-    check_dev(reward, "reward", at::kFloat, T * s.B, state);
-    check_dev(terminated, "terminated", at::kByte, T * s.B, state);
-    check_dev(win, "win", at::kByte, T * s.B, state);
     check_outputs(c, state, T, obs, state_out);
-    const cs_epsilon sched = schedule_of(epsilon, eps_env, anneal, min_epsilon, per_step, eps_trace, T, s.B, state);
-    ok(cs_rollout_policy_flight(&c, state.data_ptr(), packed.data_ptr<float>(), c1w.data_ptr<float>(), c1b.data_ptr<float>(),
-                                c2w.data_ptr<float>(), c2b.data_ptr<float>(), lw.data_ptr<float>(), lb.data_ptr<float>(),
-                                hidden.data_ptr<float>(), last.data_ptr<int64_t>(), scratch.data_ptr<float>(), (int)T, (int)flags,
-                                &sched, (uint64_t)seed, (uint32_t)step0, (uint64_t)row0, (int)select,
-                                actions.data_ptr<int64_t>(), reward.data_ptr<float>(), terminated.data_ptr<uint8_t>(),
-                                win.data_ptr<uint8_t>(), opt_ptr<float>(obs), opt_ptr<float>(state_out), stream_of(state)));
+    flight_closed_loop(&cs_rollout_policy_flight, c, state, packed, c1w, c1b, c2w, c2b, lw, lb, hidden, last, scratch, T, flags, epsilon,
+                       eps_env, anneal, min_epsilon, per_step, eps_trace, seed, step0, row0, select, actions, reward, terminated, win,
+                       opt_ptr<float>(obs), opt_ptr<float>(state_out));
 }
 
 // flight: rollout_policy_flight without observation rows that also fills the map-once tables (cs_collect_flight):
@@ -427,31 +434,12 @@ void collect_flight(const Tensor &cfg, Tensor state, const Tensor &packed, const
     const cs_config &c = config_of(cfg);
     check_state(c, state);
     const Shapes s = shapes_of(c);
-    TORCH_CHECK(T >= 1, "coopsearch: T must be >= 1");
     TORCH_CHECK(c.variant == 1, "coopsearch: collect_flight is for the flight variant");
-    check_f32(packed, "packed", (int64_t)cs_policy_packed_floats(), state);
-    check_f32(c1w, "conv1.weight", 4 * 16, state);
-    check_f32(c1b, "conv1.bias", 4, state);
-    check_f32(c2w, "conv2.weight", 4 * 9, state);
-    check_f32(c2b, "conv2.bias", 1, state);
-    check_f32(lw, "linear.weight", 16 * 576, state);
-    check_f32(lb, "linear.bias", 16, state);
-    check_f32(hidden, "hidden", s.B * s.n * 64, state);
-    check_dev(last, "last", at::kLong, s.B * s.n, state);
-    check_f32(scratch, "scratch", s.B * (16 + 4 * s.n), state);
-    check_dev(actions, "actions", at::kLong, T * s.B * s.n, state);
-    check_dev(reward, "reward", at::kFloat, T * s.B, state);
-    check_dev(terminated, "terminated", at::kByte, T * s.B, state);
-    check_dev(win, "win", at::kByte, T * s.B, state);
     check_f32(map_tab, "map_tab", (T + 1) * s.B * (s.obs_w - 4), state);
     check_f32(state_tab, "state_tab", (T + 1) * s.B * s.state_w, state);
-    const cs_epsilon sched = schedule_of(epsilon, eps_env, anneal, min_epsilon, per_step, eps_trace, T, s.B, state);
-    ok(cs_collect_flight(&c, state.data_ptr(), packed.data_ptr<float>(), c1w.data_ptr<float>(), c1b.data_ptr<float>(),
-                         c2w.data_ptr<float>(), c2b.data_ptr<float>(), lw.data_ptr<float>(), lb.data_ptr<float>(),
-                         hidden.data_ptr<float>(), last.data_ptr<int64_t>(), scratch.data_ptr<float>(), (int)T, (int)flags, &sched,
-                         (uint64_t)seed, (uint32_t)step0, (uint64_t)row0, (int)select, actions.data_ptr<int64_t>(),
-                         reward.data_ptr<float>(), terminated.data_ptr<uint8_t>(), win.data_ptr<uint8_t>(),
-                         map_tab.data_ptr<float>(), state_tab.data_ptr<float>(), stream_of(state)));
+    flight_closed_loop(&cs_collect_flight, c, state, packed, c1w, c1b, c2w, c2b, lw, lb, hidden, last, scratch, T, flags, epsilon,
+                       eps_env, anneal, min_epsilon, per_step, eps_trace, seed, step0, row0, select, actions, reward, terminated, win,
+                       map_tab.data_ptr<float>(), state_tab.data_ptr<float>());
 }
 
 // common/rollout.py:66-76,105-132 + replay_buffer.py:41-61: step-major tables -> the 11-key episode batch (cs_store_episodes);

@@ -64,8 +64,8 @@ class BatchedFlightEnv:
                 no terminal guard
     auto_reset  terminated envs are reset(init=False) at the start of the next step()
     binding     "torch" (default): the calls go through torch.ops.coopsearch.* (csrc/torch_ops.cpp: tensor checks in C++,
-                torch's current HIP stream); "ctypes": straight to the C ABI with data_ptr()s -- same library, same
-                kernels, no torch in the call path
+                torch's current HIP stream); "ctypes": the same calls on `_lib.CtypesOps`, straight to the C ABI with
+                the tensors' addresses -- same library, same kernels, no tensor checks
     kernel      flight_easy only: "group" (16 lanes per env: lowest step latency; a rollout is T launches of the step
                 kernel), "oct" (rollout only: 8 lanes per env, lane t owns agent t and targets t, t + 8), "od"
                 (rollout only: the octet layout with a kinematics wavefront running steps ahead of a detection
@@ -120,10 +120,9 @@ class BatchedFlightEnv:
             raise Exception("No such agent mode")
         self.circle_dict = circle_dict if circle_dict is not None else default_circle_dict()
         self.cfg = _cfg_from_args(args, self.circle_dict, self.batch, 1 if self.flight else 0)
-        self._cfgp = C.byref(self.cfg)
         self._cfg_t = torch.frombuffer(bytearray(bytes(self.cfg)), dtype=torch.uint8)   # the struct's bytes, for the ops
         lay = _lib.CsLayout()
-        self._call(self._L.cs_state_layout, self._cfgp, C.byref(lay))
+        _lib.check(self._L.cs_state_layout(C.byref(self.cfg), C.byref(lay)))
         self.layout = lay
         B, n, m = self.batch, self.n_agents, self.target_num
         self.cells = self.map_size * self.map_size
@@ -149,26 +148,14 @@ class BatchedFlightEnv:
         if self.freeze_done and self.auto_reset:
             self.freeze_done = False
         self.env_offset = int(env_offset)
-        if self._ops is not None:
-            assert int(self._ops.state_bytes(self._cfg_t)) == lay.total_bytes
-            self._ops.env_init(self._cfg_t, self._blob)
-        else:
-            self._call(self._L.cs_init, self._cfgp, self._blob.data_ptr(), self._stream())
+        assert int(self._ops.state_bytes(self._cfg_t)) == lay.total_bytes
+        self._ops.env_init(self._cfg_t, self._blob)
         if seeds is None:
             seeds = (DEFAULT_BASE_SEED + self.env_offset + np.arange(B, dtype=np.int64)) % (1 << 32)
         self.seed(seeds)
         self.reset(init=True)  # FlightSearchEnvEasy.__init__ ends with self.reset(init=True), :68
 
     # ------------------------------------------------------------------------------------------------ plumbing
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    def _call(self, fn, *args):
-        """ctypes route: the cs_* entry points launch on the process's current device, so the env's device is made current
-        for the call (the torch ops do the same in C++ with a HIPGuard); an env on cuda:1 works while cuda:0 is current."""
-        with torch.cuda.device(self.device):
-            _lib.check(fn(*args))
-
     def _view(self, off, count, dtype, shape):
         itemsize = torch.empty((), dtype=dtype).element_size()
         return self._blob[off:off + count * itemsize].view(dtype).view(*shape)
@@ -190,20 +177,14 @@ class BatchedFlightEnv:
     def mt_advance(self, min_ahead=400):
         """cs_mt_advance: rows with fewer than `min_ahead` twisted words ahead of their cursor are twisted fully ahead and
         their hit tapes rebuilt (when, never what: the streams are untouched)."""
-        if self._ops is not None:
-            self._ops.mt_advance(self._cfg_t, self._blob, int(min_ahead))
-        else:
-            self._call(self._L.cs_mt_advance, self._cfgp, self._blob.data_ptr(), int(min_ahead), self._stream())
+        self._ops.mt_advance(self._cfg_t, self._blob, int(min_ahead))
         self._steps_since_advance = 0
 
     def mt_canonical(self):
         """int32 [B, MT_STRIDE]: every env's MT19937 row in a form that depends only on the stream position (the kernels may
         leave different amounts of the row pre-twisted ahead of the cursor; see cs_mt_canonical)."""
         out = torch.empty(self.batch, _lib.MT_STRIDE, dtype=torch.int32, device=self.device)
-        if self._ops is not None:
-            self._ops.mt_canonical(self._cfg_t, self._blob, out)
-        else:
-            self._call(self._L.cs_mt_canonical, self._cfgp, self._blob.data_ptr(), out.data_ptr(), self._stream())
+        self._ops.mt_canonical(self._cfg_t, self._blob, out)
         return out
 
     def seed(self, seeds):
@@ -212,10 +193,7 @@ class BatchedFlightEnv:
         if s.shape != (self.batch,):
             raise ValueError("seeds must have shape (batch,)")
         t = torch.from_numpy(s.view(np.int32)).to(self.device)
-        if self._ops is not None:
-            self._ops.env_seed(self._cfg_t, self._blob, t)
-        else:
-            self._call(self._L.cs_seed, self._cfgp, self._blob.data_ptr(), t.data_ptr(), self._stream())
+        self._ops.env_seed(self._cfg_t, self._blob, t)
         self._seeds_keepalive = t
 
     # ------------------------------------------------------------------------------------------- reference API
@@ -226,7 +204,6 @@ class BatchedFlightEnv:
 
     def reset(self, init=False, mask=None):
         """env.reset(init) for every env (or those with mask[b] != 0).  flight: init=True clears the map."""
-        mptr = None
         if mask is not None:
             mask = torch.as_tensor(mask, device=self.device)
             if mask.dtype != torch.uint8:
@@ -234,12 +211,7 @@ class BatchedFlightEnv:
             mask = mask.contiguous()
             if mask.shape != (self.batch,):
                 raise ValueError("mask must have shape (batch,)")
-            mptr = mask.data_ptr()
-        if self._ops is not None:
-            self._ops.env_reset(self._cfg_t, self._blob, mask, bool(init), self._obs, self._state)
-            return
-        self._call(self._L.cs_reset, self._cfgp, self._blob.data_ptr(), mptr, 1 if init else 0,
-                                    self._obs.data_ptr(), self._state.data_ptr(), self._stream())
+        self._ops.env_reset(self._cfg_t, self._blob, mask, bool(init), self._obs, self._state)
 
     def _actions(self, actions, lead_shape):
         if not torch.is_tensor(actions):
@@ -262,10 +234,8 @@ class BatchedFlightEnv:
             f |= _lib.AUTO_RESET
         if actions.dtype == torch.int64:
             f |= _lib.ACTIONS_I64
-        if self.check_actions:
-            f |= _lib.CHECK_ACTIONS
-        elif self.binding == "torch":   # the op layer applies its own default unless told: off means off (csrc/torch_ops.cpp)
-            f |= _lib.OP_NO_CHECK_ACTIONS
+        # the ops apply their own default unless told: off means off (action_flags, csrc/torch_ops.cpp)
+        f |= _lib.CHECK_ACTIONS if self.check_actions else _lib.OP_NO_CHECK_ACTIONS
         if self.kernel == "group":
             f |= _lib.KERNEL_GROUP
         elif self.kernel == "lane":   # one env per lane, first generation (k_rollout_lane)
@@ -303,13 +273,8 @@ class BatchedFlightEnv:
         if self.step_advance and self._steps_since_advance >= STEP_ADVANCE_EVERY and self.n_agents <= 5:
             self.mt_advance(STEP_ADVANCE_MIN_AHEAD)
         self._steps_since_advance += 1
-        if self._ops is not None:
-            self._ops.env_step(self._cfg_t, self._blob, a, self._flags(a), dst["reward"], dst["terminated"].view(torch.uint8),
-                               dst["win"].view(torch.uint8), dst["obs"], dst["state"])
-        else:
-            self._call(self._L.cs_step, self._cfgp, self._blob.data_ptr(), a.data_ptr(), self._flags(a),
-                                       dst["reward"].data_ptr(), dst["terminated"].data_ptr(), dst["win"].data_ptr(),
-                                       dst["obs"].data_ptr(), dst["state"].data_ptr(), self._stream())
+        self._ops.env_step(self._cfg_t, self._blob, a, self._flags(a), dst["reward"], dst["terminated"].view(torch.uint8),
+                           dst["win"].view(torch.uint8), dst["obs"], dst["state"])
         return dst["reward"], dst["terminated"].view(torch.bool), dst["win"].view(torch.bool)
 
     def rollout(self, actions, emit=True, out=None, update_views=True):
@@ -334,14 +299,8 @@ class BatchedFlightEnv:
             out = dict(out)
         term = out["terminated"].view(torch.uint8)
         win = out["win"].view(torch.uint8)
-        if self._ops is not None:
-            self._ops.env_rollout(self._cfg_t, self._blob, a, self._flags(a), out["reward"], term, win,
-                                  out["obs"] if emit else None, out["state"] if emit else None)
-        else:
-            self._call(self._L.cs_rollout, self._cfgp, self._blob.data_ptr(), a.data_ptr(), T, self._flags(a),
-                                          out["reward"].data_ptr(), term.data_ptr(), win.data_ptr(),
-                                          out["obs"].data_ptr() if emit else None,
-                                          out["state"].data_ptr() if emit else None, self._stream())
+        self._ops.env_rollout(self._cfg_t, self._blob, a, self._flags(a), out["reward"], term, win,
+                              out["obs"] if emit else None, out["state"] if emit else None)
         if update_views:
             if emit:
                 self._obs.copy_(out["obs"][-1])
@@ -357,11 +316,7 @@ class BatchedFlightEnv:
         the NEXT step() will execute anneal -- eps = eps - anneal if eps > min_epsilon else eps, common/rollout.py:75-76 --;
         trace_row (float64 [B]) receives the values before the anneal.  Call between choose_action and step."""
         flags = (_lib.FREEZE_DONE if self.freeze_done else 0) | (_lib.AUTO_RESET if self.auto_reset else 0)
-        if self._ops is not None:
-            self._ops.epsilon_step(self._cfg_t, self._blob, flags, eps_env, float(anneal), float(min_epsilon), trace_row)
-            return
-        self._call(self._L.cs_epsilon_step, self._cfgp, self._blob.data_ptr(), flags, eps_env.data_ptr(), float(anneal),
-                   float(min_epsilon), trace_row.data_ptr() if trace_row is not None else None, self._stream())
+        self._ops.epsilon_step(self._cfg_t, self._blob, flags, eps_env, float(anneal), float(min_epsilon), trace_row)
 
     def rollout_policy(self, agents, T, epsilon=0.0, evaluate=True, emit=True, out=None, update_views=True, eps_env=None,
                        anneal=0.0, min_epsilon=0.0, per_step=False, eps_trace=None):
@@ -381,61 +336,19 @@ class BatchedFlightEnv:
         if agents.rows != B * n or bool(getattr(agents, "conv", False)) != self.flight:
             raise ValueError("rollout_policy: `agents` must be a FusedAgents for this env's batch "
                              "(with the conv front end for flight, without it for flight_easy)")
-        out = dict(out) if out else {}
-        dev = self.device
         spec = dict(reward=((T, B), torch.float32), terminated=((T, B), torch.uint8), win=((T, B), torch.uint8),
                     actions=((T, B, n), torch.int64))
-        if emit or out.get("obs") is not None:
+        if emit or (out and out.get("obs") is not None):
             spec.update(obs=((T, B, n, self.obs_width), torch.float32), state=((T, B, self.state_shape), torch.float32))
-        for k, (shape, dt) in spec.items():
-            if out.get(k) is None:
-                out[k] = torch.empty(shape, dtype=dt, device=dev)
-            elif out[k].numel() * out[k].element_size() != torch.Size(shape).numel() * dt.itemsize or not out[k].is_contiguous():
-                raise ValueError(f"rollout_policy(out=): bad destination for {k!r}")
+        out, scratch, tail = self._closed_loop("rollout_policy", agents, T, spec, out, epsilon, evaluate, eps_env, anneal,
+                                               min_epsilon, per_step, eps_trace)
         has_obs = out.get("obs") is not None and out.get("state") is not None
-        flags = (_lib.FREEZE_DONE if self.freeze_done else 0) | (_lib.AUTO_RESET if self.auto_reset else 0)
-        sel_eps, sel_flags = agents.selection(epsilon, evaluate)
-        if evaluate and not agents.softmax:
-            eps_env = eps_trace = None   # epsilon = 0 if evaluate (rollout.py:35): no schedule
-        if eps_trace is not None and eps_env is None:
-            raise ValueError("rollout_policy: eps_trace needs eps_env")
-        for name, tns, numel in (("eps_env", eps_env, B), ("eps_trace", eps_trace, T * B)):
-            if tns is not None and (tns.dtype != torch.float64 or tns.numel() != numel or not tns.is_contiguous() or not tns.is_cuda
-                                    or (tns.device.index or 0) != (dev.index or 0)):
-                raise ValueError(f"rollout_policy: {name} must be a contiguous float64 device tensor of {numel} elements")
-        sched_t = (sel_eps, eps_env, float(anneal), float(min_epsilon), bool(per_step), eps_trace)
-        if self._ops is None:
-            sched_c = _lib.CsEpsilon(sel_eps, float(anneal), float(min_epsilon), 1 if per_step else 0, 0,
-                                     eps_env.data_ptr() if eps_env is not None else None,
-                                     eps_trace.data_ptr() if eps_trace is not None else None)
+        tail += (out["obs"] if has_obs else None, out["state"] if has_obs else None)
         if self.flight:
-            scratch = getattr(agents, "_flight_scratch", None)
-            if scratch is None or scratch.numel() != B * (16 + 4 * n):
-                scratch = agents._flight_scratch = torch.empty(B, 16 + 4 * n, dtype=torch.float32, device=dev)
-            if self._ops is not None:
-                self._ops.rollout_policy_flight(self._cfg_t, self._blob, agents.packed, *agents.conv_w, agents.hidden,
-                                                agents.actions, scratch, T, flags, *sched_t, agents.seed, agents.calls,
-                                                agents.row0, sel_flags, out["actions"], out["reward"],
-                                                out["terminated"].view(torch.uint8), out["win"].view(torch.uint8),
-                                                out["obs"] if has_obs else None, out["state"] if has_obs else None)
-            else:
-                self._call(self._L.cs_rollout_policy_flight,
-                    self._cfgp, self._blob.data_ptr(), agents.packed.data_ptr(), *[w.data_ptr() for w in agents.conv_w],
-                    agents.hidden.data_ptr(), agents.actions.data_ptr(), scratch.data_ptr(), T, flags, C.byref(sched_c), agents.seed,
-                    agents.calls, agents.row0, sel_flags, out["actions"].data_ptr(), out["reward"].data_ptr(),
-                    out["terminated"].data_ptr(), out["win"].data_ptr(), out["obs"].data_ptr() if has_obs else None,
-                    out["state"].data_ptr() if has_obs else None, self._stream())
-        elif self._ops is not None:
-            self._ops.rollout_policy(self._cfg_t, self._blob, agents.packed, agents.hidden, agents.actions, T, flags, *sched_t,
-                                     agents.seed, agents.calls, agents.row0, sel_flags, out["actions"], out["reward"],
-                                     out["terminated"].view(torch.uint8), out["win"].view(torch.uint8),
-                                     out["obs"] if has_obs else None, out["state"] if has_obs else None)
+            self._ops.rollout_policy_flight(self._cfg_t, self._blob, agents.packed, *agents.conv_w, agents.hidden,
+                                            agents.actions, scratch, *tail)
         else:
-            self._call(self._L.cs_rollout_policy,
-                self._cfgp, self._blob.data_ptr(), agents.packed.data_ptr(), agents.hidden.data_ptr(),
-                agents.actions.data_ptr(), T, flags, C.byref(sched_c), agents.seed, agents.calls, agents.row0, sel_flags,
-                out["actions"].data_ptr(), out["reward"].data_ptr(), out["terminated"].data_ptr(), out["win"].data_ptr(),
-                out["obs"].data_ptr() if has_obs else None, out["state"].data_ptr() if has_obs else None, self._stream())
+            self._ops.rollout_policy(self._cfg_t, self._blob, agents.packed, agents.hidden, agents.actions, *tail)
         agents.calls += T
         agents.actions.copy_(out["actions"][-1])
         if update_views:
@@ -444,9 +357,36 @@ class BatchedFlightEnv:
                 self._state.copy_(out["state"][-1])
             else:
                 self.refresh()
-        out["terminated"] = out["terminated"].view(torch.bool)
-        out["win"] = out["win"].view(torch.bool)
         return out
+
+    def _closed_loop(self, who, agents, T, spec, out, epsilon, evaluate, eps_env, anneal, min_epsilon, per_step, eps_trace):
+        """What rollout_policy and collect_flight (`who`, for the messages) do before their call: the outputs of `spec`
+        ({key: (shape, dtype)}) allocated or validated, the schedule validated, flight's scratch tensor.  -> (out, scratch, the
+        ops' arguments from T to win); out's terminated / win are bool views of the uint8 tensors the call writes."""
+        B, n, dev = self.batch, self.n_agents, self.device
+        out = dict(out) if out else {}
+        for k, (shape, dt) in spec.items():
+            if out.get(k) is None:
+                out[k] = torch.empty(shape, dtype=dt, device=dev)
+            elif out[k].numel() * out[k].element_size() != torch.Size(shape).numel() * dt.itemsize or not out[k].is_contiguous():
+                raise ValueError(f"{who}(out=): bad destination for {k!r}")
+        flags = (_lib.FREEZE_DONE if self.freeze_done else 0) | (_lib.AUTO_RESET if self.auto_reset else 0)
+        sel_eps, sel_flags = agents.selection(epsilon, evaluate)
+        if evaluate and not agents.softmax:
+            eps_env = eps_trace = None   # epsilon = 0 if evaluate (rollout.py:35): no schedule
+        if eps_trace is not None and eps_env is None:
+            raise ValueError(f"{who}: eps_trace needs eps_env")
+        for name, tns, numel in (("eps_env", eps_env, B), ("eps_trace", eps_trace, T * B)):
+            if tns is not None and (tns.dtype != torch.float64 or tns.numel() != numel or not tns.is_contiguous() or not tns.is_cuda
+                                    or (tns.device.index or 0) != (dev.index or 0)):
+                raise ValueError(f"{who}: {name} must be a contiguous float64 device tensor of {numel} elements")
+        scratch = getattr(agents, "_flight_scratch", None) if self.flight else None
+        if self.flight and (scratch is None or scratch.numel() != B * (16 + 4 * n)):
+            scratch = agents._flight_scratch = torch.empty(B, 16 + 4 * n, dtype=torch.float32, device=dev)
+        term, win = out["terminated"].view(torch.uint8), out["win"].view(torch.uint8)
+        out["terminated"], out["win"] = term.view(torch.bool), win.view(torch.bool)
+        return out, scratch, (T, flags, sel_eps, eps_env, float(anneal), float(min_epsilon), bool(per_step), eps_trace, agents.seed,
+                              agents.calls, agents.row0, sel_flags, out["actions"], out["reward"], term, win)
 
     def collect_flight(self, agents, T, epsilon=0.0, evaluate=True, out=None, update_views=True, eps_env=None, anneal=0.0,
                        min_epsilon=0.0, per_step=False, eps_trace=None):
@@ -459,61 +399,25 @@ class BatchedFlightEnv:
         if not self.flight:
             raise ValueError("collect_flight: the flight variant only (flight_easy observations carry no map)")
         T = int(T)
-        B, n, dev = self.batch, self.n_agents, self.device
+        B, n = self.batch, self.n_agents
         if agents.rows != B * n or not bool(getattr(agents, "conv", False)):
             raise ValueError("collect_flight: `agents` must be a FusedAgents with the conv front end for this env's batch")
-        out = dict(out) if out else {}
         spec = dict(reward=((T, B), torch.float32), terminated=((T, B), torch.uint8), win=((T, B), torch.uint8),
                     actions=((T, B, n), torch.int64), map=((T + 1, B, self.cells), torch.float32),
                     state=((T + 1, B, self.state_shape), torch.float32))
-        for k, (shape, dt) in spec.items():
-            if out.get(k) is None:
-                out[k] = torch.empty(shape, dtype=dt, device=dev)
-            elif out[k].numel() * out[k].element_size() != torch.Size(shape).numel() * dt.itemsize or not out[k].is_contiguous():
-                raise ValueError(f"collect_flight(out=): bad destination for {k!r}")
-        flags = (_lib.FREEZE_DONE if self.freeze_done else 0) | (_lib.AUTO_RESET if self.auto_reset else 0)
-        sel_eps, sel_flags = agents.selection(epsilon, evaluate)
-        if evaluate and not agents.softmax:
-            eps_env = eps_trace = None   # epsilon = 0 if evaluate (rollout.py:35): no schedule
-        if eps_trace is not None and eps_env is None:
-            raise ValueError("collect_flight: eps_trace needs eps_env")
-        for name, tns, numel in (("eps_env", eps_env, B), ("eps_trace", eps_trace, T * B)):
-            if tns is not None and (tns.dtype != torch.float64 or tns.numel() != numel or not tns.is_contiguous() or not tns.is_cuda
-                                    or (tns.device.index or 0) != (dev.index or 0)):
-                raise ValueError(f"collect_flight: {name} must be a contiguous float64 device tensor of {numel} elements")
-        scratch = getattr(agents, "_flight_scratch", None)
-        if scratch is None or scratch.numel() != B * (16 + 4 * n):
-            scratch = agents._flight_scratch = torch.empty(B, 16 + 4 * n, dtype=torch.float32, device=dev)
-        term, win = out["terminated"].view(torch.uint8), out["win"].view(torch.uint8)
-        if self._ops is not None:
-            self._ops.collect_flight(self._cfg_t, self._blob, agents.packed, *agents.conv_w, agents.hidden, agents.actions, scratch,
-                                     T, flags, sel_eps, eps_env, float(anneal), float(min_epsilon), bool(per_step), eps_trace,
-                                     agents.seed, agents.calls, agents.row0, sel_flags, out["actions"], out["reward"], term, win,
-                                     out["map"], out["state"])
-        else:
-            sched_c = _lib.CsEpsilon(sel_eps, float(anneal), float(min_epsilon), 1 if per_step else 0, 0,
-                                     eps_env.data_ptr() if eps_env is not None else None,
-                                     eps_trace.data_ptr() if eps_trace is not None else None)
-            self._call(self._L.cs_collect_flight,
-                self._cfgp, self._blob.data_ptr(), agents.packed.data_ptr(), *[w.data_ptr() for w in agents.conv_w],
-                agents.hidden.data_ptr(), agents.actions.data_ptr(), scratch.data_ptr(), T, flags, C.byref(sched_c), agents.seed,
-                agents.calls, agents.row0, sel_flags, out["actions"].data_ptr(), out["reward"].data_ptr(), term.data_ptr(),
-                win.data_ptr(), out["map"].data_ptr(), out["state"].data_ptr(), self._stream())
+        out, scratch, tail = self._closed_loop("collect_flight", agents, T, spec, out, epsilon, evaluate, eps_env, anneal,
+                                               min_epsilon, per_step, eps_trace)
+        self._ops.collect_flight(self._cfg_t, self._blob, agents.packed, *agents.conv_w, agents.hidden, agents.actions, scratch,
+                                 *tail, out["map"], out["state"])
         agents.calls += T
         agents.actions.copy_(out["actions"][-1])
         if update_views:
             self.refresh()
-        out["terminated"] = term.view(torch.bool)
-        out["win"] = win.view(torch.bool)
         return out
 
     def refresh(self):
         """Re-emit get_obs()/get_state() from the device state (after editing raw())."""
-        if self._ops is not None:
-            self._ops.env_emit(self._cfg_t, self._blob, self._obs, self._state)
-            return
-        self._call(self._L.cs_emit, self._cfgp, self._blob.data_ptr(), self._obs.data_ptr(), self._state.data_ptr(),
-                                   self._stream())
+        self._ops.env_emit(self._cfg_t, self._blob, self._obs, self._state)
 
     def get_obs(self):
         """[B, n, 4] (flight: [B, n, map*map + 4], map first) float32 -- live buffer."""
@@ -552,10 +456,7 @@ class BatchedFlightEnv:
     def metric_partials(self):
         """float64[4] on device: sum total_reward, sum win, sum target_find, env count (runner.py:86-96)."""
         self._metrics.zero_()
-        if self._ops is not None:
-            self._ops.env_metrics(self._cfg_t, self._blob, self._metrics)
-            return self._metrics
-        self._call(self._L.cs_metrics, self._cfgp, self._blob.data_ptr(), self._metrics.data_ptr(), self._stream())
+        self._ops.env_metrics(self._cfg_t, self._blob, self._metrics)
         return self._metrics
 
     def render(self, env=0, path=None, pause=None):

@@ -84,7 +84,8 @@ def test_staleness_is_decided_by_source_content_not_mtime(tmp_path, monkeypatch)
 def test_binding_falls_back_to_ctypes_only_when_torch_was_not_asked_for(monkeypatch):
     """without g++ / torch headers the default binding degrades to ctypes (same library, same kernels) with a
     warning; an explicit binding='torch' raises."""
-    assert _lib.pick_binding("ctypes") == ("ctypes", None)
+    name, ops = _lib.pick_binding("ctypes")
+    assert name == "ctypes" and isinstance(ops, _lib.CtypesOps) and ops is _lib.ctypes_ops()
     name, ops = _lib.pick_binding(None)
     assert name == "torch" and ops is _lib.torch_ops()
 
@@ -92,11 +93,33 @@ def test_binding_falls_back_to_ctypes_only_when_torch_was_not_asked_for(monkeypa
         raise _lib.CoopSearchError("coopsearch_torch.so is missing and there is no g++ to build it")
     monkeypatch.setattr(_lib, "torch_ops", broken)
     with pytest.warns(RuntimeWarning, match="using the ctypes binding"):
-        assert _lib.pick_binding(None) == ("ctypes", None)
+        name, ops = _lib.pick_binding(None)
+    assert name == "ctypes" and isinstance(ops, _lib.CtypesOps)
     with pytest.raises(_lib.CoopSearchError):
         _lib.pick_binding("torch")
     with pytest.raises(ValueError):
         _lib.pick_binding("pybind")
+
+
+def test_ctypes_ops_mirror_the_torch_ops_by_name_and_argument():
+    """The package calls ONE ops object, torch.ops.coopsearch or _lib.CtypesOps: every public method of the ctypes twin is an
+    op of that name whose registered schema has the same argument names in the same order, and every op that env.py, agents.py
+    or collector.py calls has a twin."""
+    import inspect
+    ops = _lib.torch_ops()
+    twins = {k: v for k, v in vars(_lib.CtypesOps).items() if not k.startswith("_") and callable(v)}
+    assert len(twins) == 19
+    for name, fn in twins.items():
+        assert hasattr(ops, name), name
+        schema = getattr(ops, name).default._schema
+        assert [a.name for a in schema.arguments] == list(inspect.signature(fn).parameters)[1:], name
+    pkg = os.path.join(ROOT, "cooperative-search_amd")
+    called = set()
+    for fn in ("env.py", "agents.py", "collector.py"):
+        txt = open(os.path.join(pkg, fn)).read()
+        assert "data_ptr()" not in txt and "_ops is None" not in txt and "_ops is not None" not in txt, fn
+        called |= set(re.findall(r"(?:_ops|pick_binding\(None\)\[1\])\.([a-z_0-9]+)\(", txt))
+    assert called == set(twins), called ^ set(twins)   # a twin for every op called, and none that nobody calls
 
 
 def _cfg(**kw):

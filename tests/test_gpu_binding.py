@@ -19,7 +19,8 @@ def test_torch_ops_and_ctypes_bindings_agree(env_name):
     seeds = np.arange(B, dtype=np.uint32) + 17
     envs = [cs.BatchedFlightEnv(args, batch=B, seeds=seeds, freeze_done=False, auto_reset=True, binding=b)
             for b in ("torch", "ctypes")]
-    assert envs[0]._ops is not None and envs[1]._ops is None
+    assert envs[0]._ops is _lib.torch_ops() and envs[0].binding == "torch"
+    assert isinstance(envs[1]._ops, _lib.CtypesOps) and envs[1].binding == "ctypes"
     g = torch.Generator("cuda").manual_seed(9)
     for t in range(T):
         a = torch.randint(0, 3, (B, n), dtype=torch.int64 if t % 2 else torch.int32, device="cuda", generator=g)
@@ -105,7 +106,7 @@ def test_caller_side_ops_agree_with_ctypes_and_check_their_tensors(monkeypatch):
     cs.apply_env_info(args, env_t)
     torch.manual_seed(2)
     ag_t = FusedAgents(args, B, seed=9)
-    assert ag_t._ops is not None
+    assert ag_t._ops is _lib.torch_ops()
     out_t = env_t.rollout_policy(ag_t, T, epsilon=0.2, evaluate=False)
     ep_t = collector.assemble_episodes(torch.cat([out_t["obs"][:1] * 0, out_t["obs"]]), torch.cat([out_t["state"][:1] * 0, out_t["state"]]),
                                        out_t["actions"], out_t["reward"], out_t["terminated"], 3)
@@ -113,7 +114,7 @@ def test_caller_side_ops_agree_with_ctypes_and_check_their_tensors(monkeypatch):
     monkeypatch.setenv("COOPSEARCH_LIB", _lib.library_path())
     env_c = cs.BatchedFlightEnv(args, batch=B, freeze_done=True)
     ag_c = FusedAgents(args, B, net=ag_t.net, seed=9)
-    assert env_c._ops is None and ag_c._ops is None
+    assert isinstance(env_c._ops, _lib.CtypesOps) and env_c.binding == "ctypes" and isinstance(ag_c._ops, _lib.CtypesOps)
     out_c = env_c.rollout_policy(ag_c, T, epsilon=0.2, evaluate=False)
     ep_c = collector.assemble_episodes(torch.cat([out_c["obs"][:1] * 0, out_c["obs"]]), torch.cat([out_c["state"][:1] * 0, out_c["state"]]),
                                        out_c["actions"], out_c["reward"], out_c["terminated"], 3)
@@ -146,8 +147,11 @@ def test_caller_side_ops_agree_with_ctypes_and_check_their_tensors(monkeypatch):
 
 @pytest.mark.parametrize("emit", [True, False])
 def test_flight_closed_loop_call_agrees_between_bindings(monkeypatch, emit):
-    """cs_rollout_policy_flight through torch.ops.coopsearch.rollout_policy_flight and through ctypes; the op layer
-    refuses a scratch tensor of the wrong size."""
+    """cs_rollout_policy_flight through torch.ops.coopsearch.rollout_policy_flight and through ctypes, then the calls of the
+    flight training path -- collect_flight, assemble_episodes_compact, sync_weights of a changed network, forward_raw -- the
+    same way: every result bit for bit; the op layer refuses a scratch tensor of the wrong size."""
+    import copy
+    from cooperative_search_amd import collector
     from cooperative_search_amd.agents import FusedAgents
     n, B, T = 3, 48, 12
     args = cs.make_env_args("flight", n_agents=n)
@@ -156,16 +160,44 @@ def test_flight_closed_loop_call_agrees_between_bindings(monkeypatch, emit):
     cs.apply_env_info(args, env_t)
     torch.manual_seed(4)
     ag_t = FusedAgents(args, B, seed=3)
-    assert ag_t._ops is not None
-    out_t = env_t.rollout_policy(ag_t, T, epsilon=0.2, evaluate=False, emit=emit)
+    assert ag_t._ops is _lib.torch_ops()
+    net_c = copy.deepcopy(ag_t.net)   # run() changes the network it is given
+    x = torch.rand(B * n, env_t.cells + 4 + 3 + n, device="cuda", generator=torch.Generator("cuda").manual_seed(6))
+
+    def run(env, ag):
+        out = env.rollout_policy(ag, T, epsilon=0.2, evaluate=False, emit=emit)
+        after = dict(hidden=ag.hidden.clone(), prob=env.raw()["prob"].clone(), obs=env.get_obs().clone())
+        col = env.collect_flight(ag, T, epsilon=0.2, evaluate=False)
+        ep = collector.assemble_episodes_compact(col["map"], col["state"], col["actions"], col["reward"], col["terminated"])
+        with torch.no_grad():
+            for p in ag.net.parameters():
+                p.mul_(1.25)
+        before = ag.packed.clone()
+        ag.sync_weights()
+        assert not torch.equal(ag.packed, before)
+        acts = ag.forward_raw(x).clone()
+        return out, after, col, ep, acts
+
+    res_t = run(env_t, ag_t)
     monkeypatch.setenv("COOPSEARCH_LIB", _lib.library_path())
     env_c = cs.BatchedFlightEnv(args, batch=B, freeze_done=False, auto_reset=True)
-    ag_c = FusedAgents(args, B, net=ag_t.net, seed=3)
-    assert env_c._ops is None and ag_c._ops is None
-    out_c = env_c.rollout_policy(ag_c, T, epsilon=0.2, evaluate=False, emit=emit)
+    ag_c = FusedAgents(args, B, net=net_c, seed=3)
+    assert isinstance(env_c._ops, _lib.CtypesOps) and env_c.binding == "ctypes" and isinstance(ag_c._ops, _lib.CtypesOps)
+    res_c = run(env_c, ag_c)
     monkeypatch.delenv("COOPSEARCH_LIB")
+    (out_t, after_t, col_t, ep_t, acts_t), (out_c, after_c, col_c, ep_c, acts_c) = res_t, res_c
     for k in ("actions", "reward", "terminated", "win") + (("obs", "state") if emit else ()):
         assert torch.equal(out_t[k], out_c[k]), k
+    assert torch.equal(after_t["hidden"], after_c["hidden"]) and torch.equal(after_t["prob"], after_c["prob"])
+    assert torch.equal(after_t["obs"], after_c["obs"])
+    assert set(col_t) == set(col_c) == {"actions", "reward", "terminated", "win", "map", "state"}
+    for k in col_t:
+        assert torch.equal(col_t[k], col_c[k]), k
+    assert set(ep_t) == set(ep_c) == set(collector.COMPACT_KEYS)
+    for k in ep_t:
+        assert torch.equal(ep_t[k], ep_c[k]), k
+    assert torch.equal(ag_t.packed, ag_c.packed) and torch.equal(ag_t.pack_status, ag_c.pack_status)
+    assert torch.equal(acts_t, acts_c) and torch.equal(ag_t.q, ag_c.q)
     assert torch.equal(ag_t.hidden, ag_c.hidden) and torch.equal(env_t.raw()["prob"], env_c.raw()["prob"])
     assert torch.equal(env_t.get_obs(), env_c.get_obs())
     ops = _lib.torch_ops()

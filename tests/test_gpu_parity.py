@@ -966,7 +966,7 @@ def test_mt_advance_changes_when_not_what():
         a = torch.randint(0, 3, (B, n), dtype=torch.int32, device="cuda", generator=g)
         if t % 37 == 5:
             before = e2.mt_canonical()
-            _lib.check(e2._L.cs_mt_advance(e2._cfgp, e2._blob.data_ptr(), 10 ** 6 if t % 2 else 300, e2._stream()))
+            e2.mt_advance(10 ** 6 if t % 2 else 300)
             assert torch.equal(before, e2.mt_canonical())
             assert int(e2.raw()["ahead"].max().item()) == 624
         r1, t1, w1 = e1.step(a)
