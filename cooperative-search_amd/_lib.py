@@ -20,7 +20,7 @@ SELECT_SOFTMAX, SELECT_SAMPLE = 1, 2
 FREEZE_DONE, AUTO_RESET, ACTIONS_I64, KERNEL_GROUP, KERNEL_LANE, KERNEL_SOLO, KERNEL_DUO, KERNEL_OCT, KERNEL_OD, KERNEL_ODE, KERNEL_LANEV, CHECK_ACTIONS = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048
 
 EXPORTS = ["cs_abi_version", "cs_source_hash", "cs_has_legacy_kernels", "cs_last_error", "cs_state_layout", "cs_init", "cs_seed", "cs_reset", "cs_step",
-           "cs_rollout", "cs_rollout_policy", "cs_rollout_policy_flight", "cs_collect_flight", "cs_emit", "cs_metrics", "cs_mt_canonical", "cs_mt_advance", "cs_policy_packed_floats", "cs_policy_pack", "cs_policy_pack_device", "cs_policy_forward",
+           "cs_rollout", "cs_rollout_policy", "cs_rollout_policy_flight", "cs_collect_flight", "cs_emit", "cs_snapshot_bytes", "cs_snapshot", "cs_restore", "cs_metrics", "cs_mt_canonical", "cs_mt_advance", "cs_policy_packed_floats", "cs_policy_pack", "cs_policy_pack_device", "cs_policy_forward",
            "cs_policy_conv_features", "cs_policy_conv_features_backward_scratch", "cs_policy_conv_features_backward", "cs_policy_last_error", "cs_store_episodes", "cs_store_episodes_compact", "cs_episodes_last_error", "cs_epsilon_step",
            "cs_gru_seq_forward", "cs_gru_seq_backward", "cs_episode_returns", "cs_learn_last_error"]
 
@@ -109,6 +109,10 @@ def load():
     L.cs_epsilon_step.argtypes = [C.POINTER(CsConfig), vp, C.c_int, vp, C.c_double, C.c_double, vp, vp]
     L.cs_emit.argtypes = [C.POINTER(CsConfig), vp, vp, vp, vp]
     L.cs_metrics.argtypes = [C.POINTER(CsConfig), vp, vp, vp]
+    L.cs_snapshot_bytes.argtypes = [C.POINTER(CsConfig)]
+    L.cs_snapshot_bytes.restype = C.c_size_t
+    L.cs_snapshot.argtypes = [C.POINTER(CsConfig), vp, vp, C.c_int64, vp, vp]
+    L.cs_restore.argtypes = [C.POINTER(CsConfig), vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, vp, vp]
     L.cs_mt_canonical.argtypes = [C.POINTER(CsConfig), vp, vp, vp]
     L.cs_mt_advance.argtypes = [C.POINTER(CsConfig), vp, C.c_int, vp]
     L.cs_policy_packed_floats.restype = C.c_size_t
@@ -129,7 +133,7 @@ def load():
     L.cs_episode_returns.argtypes = [vp] * 4 + [C.c_int, C.c_int, C.c_float, C.c_float, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
-        if name not in ("cs_abi_version", "cs_source_hash", "cs_has_legacy_kernels", "cs_last_error", "cs_policy_packed_floats", "cs_policy_last_error",
+        if name not in ("cs_abi_version", "cs_source_hash", "cs_has_legacy_kernels", "cs_last_error", "cs_policy_packed_floats", "cs_snapshot_bytes", "cs_policy_last_error",
                         "cs_episodes_last_error", "cs_learn_last_error"):
             fn.restype = C.c_int
     if L.cs_abi_version() != ABI_VERSION:

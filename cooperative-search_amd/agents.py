@@ -202,6 +202,21 @@ class FusedAgents:
         self.hidden.zero_()
         self.actions.fill_(-1)
 
+    def state_dict(self):
+        """What acting changes besides the network: the noise key and counter, the recurrent state, the last actions."""
+        return {"seed": int(self.seed), "calls": int(self.calls), "hidden": self.hidden.cpu(), "actions": self.actions.cpu()}
+
+    def check_state_dict(self, sd):
+        if tuple(sd["hidden"].shape) != tuple(self.hidden.shape) or tuple(sd["actions"].shape) != tuple(self.actions.shape):
+            raise ValueError(f"FusedAgents: state of {sd['hidden'].shape[0]} rows for {self.rows}")
+
+    def load_state_dict(self, sd):
+        """Takes state_dict()'s fields; the weight blob is not part of it (call sync_weights() once `net` holds its weights)."""
+        self.check_state_dict(sd)
+        self.seed, self.calls = int(sd["seed"]), int(sd["calls"])
+        self.hidden.copy_(sd["hidden"])
+        self.actions.copy_(sd["actions"])
+
     def selection(self, epsilon, evaluate):
         """(epsilon, CS_SELECT_* flags) of one choose_action call.  argmax rule (agent.py:68-75): greedy when evaluating.
         Softmax rule (:77-97): epsilon always enters prob; the draw is replaced by argmax only if epsilon == 0 and

@@ -113,6 +113,18 @@ class EpsilonSchedule:
         self.values = torch.where(v > self.min_epsilon, v - self.anneal, v)   # IEEE double subtraction, like the reference's floats
         return self.values
 
+    def state_dict(self):
+        """The mutable part: every env's current epsilon (anneal, min_epsilon and scale come from args)."""
+        return {"values": self.values.cpu()}
+
+    def check_state_dict(self, sd):
+        if tuple(sd["values"].shape) != tuple(self.values.shape):
+            raise ValueError(f"EpsilonSchedule: state of {tuple(sd['values'].shape)[0]} envs for a schedule of {self.values.shape[0]}")
+
+    def load_state_dict(self, sd):
+        self.check_state_dict(sd)
+        self.values = sd["values"].to(self.values.device, torch.float64).clone()
+
     def begin_episode(self, episode_num=None):
         """What generate_episode does to epsilon before its loop (rollout.py:36-41)."""
         if self.scale == "episode" or (self.scale == "epoch" and episode_num == 0):

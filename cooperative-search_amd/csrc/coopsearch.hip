@@ -1579,6 +1579,7 @@ __global__ __launch_bounds__(BLOCK) void k_emit(DevParams p, float *obs, float *
 }
 
 #include "flight_map.h"
+#include "snapshot.h"   // k_snapshot / k_restore: an env's logical state as one record (cs_snapshot, cs_restore)
 
 // ---------------------------------------------------------------------------------------------------------
 __global__ void k_seed(DevParams p, const uint32_t *seeds) {
@@ -2392,6 +2393,44 @@ int cs_emit(const cs_config *cfg, void *state_dev, float *obs_dev, float *state_
         CS_DISPATCH_N(cfg->n_agents, hipLaunchKernelGGL(k_map<N>, map_grid(p), dim3(MAP_BLOCK), 0, s, p, obs_dev, 0, 0));
     }
     return launched("cs_emit");
+}
+
+size_t cs_snapshot_bytes(const cs_config *cfg) {
+    if (check_config(cfg)) return 0;
+    return (size_t)SNAP_OFF_MAP + (cfg->variant == 1 ? (size_t)cfg->map_size * cfg->map_size * sizeof(float) : 0);
+}
+
+int cs_snapshot(const cs_config *cfg, const void *state_dev, const int64_t *env_idx_dev, int64_t count, void *records_dev,
+                void *stream) {
+    DevParams p;
+    int rc = make_params(cfg, const_cast<void *>(state_dev), &p);
+    if (rc) return rc;
+    if (count < 0 || count > (1ll << 27) || (!env_idx_dev && count > p.B)) return fail(CS_E_ARG, "cs_snapshot: count out of range");
+    if (count == 0) return CS_OK;
+    if (!records_dev || (reinterpret_cast<size_t>(records_dev) & 15) != 0) return fail(CS_E_ARG, "cs_snapshot: records_dev must be 16-byte aligned");
+    const SnapArgs a{reinterpret_cast<const long long *>(env_idx_dev), nullptr, count, count, cs_snapshot_bytes(cfg), cfg->n_agents};
+    hipLaunchKernelGGL(k_snapshot, dim3((unsigned)count), dim3(64), 0, (hipStream_t)stream, p, a, static_cast<unsigned char *>(records_dev));
+    return launched("cs_snapshot");
+}
+
+int cs_restore(const cs_config *cfg, void *state_dev, const void *records_dev, int64_t n_records, const int64_t *src_idx_dev,
+               const int64_t *dst_idx_dev, int64_t count, int32_t *status_dev, float *obs_dev, float *state_out_dev, void *stream) {
+    DevParams p;
+    int rc = make_params(cfg, state_dev, &p);
+    if (rc) return rc;
+    if (count < 0 || count > (1ll << 27) || n_records < 0 || (!dst_idx_dev && count > p.B) || (!src_idx_dev && count > n_records))
+        return fail(CS_E_ARG, "cs_restore: count out of range");
+    if (count > 0 && (!records_dev || (reinterpret_cast<size_t>(records_dev) & 15) != 0))
+        return fail(CS_E_ARG, "cs_restore: records_dev must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const SnapArgs a{reinterpret_cast<const long long *>(src_idx_dev), reinterpret_cast<const long long *>(dst_idx_dev), count, n_records,
+                     cs_snapshot_bytes(cfg), cfg->n_agents};
+    const unsigned char *recs = static_cast<const unsigned char *>(records_dev);
+    if (status_dev) hipLaunchKernelGGL(k_restore_check, dim3(1), dim3(1024), 0, s, p, a, recs, status_dev);
+    if (count > 0) hipLaunchKernelGGL(k_restore, dim3((unsigned)count), dim3(64), 0, s, p, a, recs);
+    rc = launched("cs_restore");
+    if (rc || (!obs_dev && !state_out_dev)) return rc;
+    return cs_emit(cfg, state_dev, obs_dev, state_out_dev, stream);
 }
 
 int cs_metrics(const cs_config *cfg, void *state_dev, double *out4_dev, void *stream) {

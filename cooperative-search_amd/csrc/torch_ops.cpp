@@ -206,6 +206,47 @@ void mt_canonical(const Tensor &cfg, Tensor state, Tensor rows_out) {
     ok(cs_mt_canonical(&c, state.data_ptr(), reinterpret_cast<uint32_t *>(rows_out.data_ptr()), stream_of(state)));
 }
 
+// ---- env snapshot / restore (cs_snapshot / cs_restore): records uint8 [count, snapshot_bytes], index tensors int64 ------------
+int64_t snapshot_bytes(const Tensor &cfg) {
+    const size_t n = cs_snapshot_bytes(&config_of(cfg));
+    TORCH_CHECK(n > 0, cs_last_error());
+    return (int64_t)n;
+}
+
+int64_t check_records(const cs_config &c, const Tensor &records, const Tensor &state) {
+    const int64_t rb = (int64_t)cs_snapshot_bytes(&c);
+    TORCH_CHECK(records.dim() == 2 && records.size(1) == rb, "coopsearch: records must be [count, ", rb, "] uint8");
+    check_dev(records, "records", at::kByte, records.size(0) * rb, state);
+    return records.size(0);
+}
+
+void env_snapshot(const Tensor &cfg, const Tensor &state, const c10::optional<Tensor> &envs, Tensor records) {
+    const cs_config &c = config_of(cfg);
+    check_state(c, state);
+    const int64_t count = check_records(c, records, state);
+    if (envs.has_value() && envs->defined()) check_dev(*envs, "envs", at::kLong, count, state);
+    else TORCH_CHECK(count <= c.batch, "coopsearch: ", count, " records for a batch of ", c.batch, " envs");
+    ok(cs_snapshot(&c, state.data_ptr(), opt_ptr<const int64_t>(envs), count, records.data_ptr(), stream_of(state)));
+}
+
+void env_restore(const Tensor &cfg, Tensor state, const Tensor &records, const c10::optional<Tensor> &src,
+                 const c10::optional<Tensor> &dst, c10::optional<Tensor> status, c10::optional<Tensor> obs,
+                 c10::optional<Tensor> state_out) {
+    const cs_config &c = config_of(cfg);
+    check_state(c, state);
+    const int64_t n_records = check_records(c, records, state);
+    const bool has_src = src.has_value() && src->defined(), has_dst = dst.has_value() && dst->defined();
+    const int64_t count = has_src ? src->numel() : (has_dst ? dst->numel() : n_records);
+    if (has_src) check_dev(*src, "src", at::kLong, count, state);
+    else TORCH_CHECK(count <= n_records, "coopsearch: ", count, " entries for ", n_records, " records");
+    if (has_dst) check_dev(*dst, "dst", at::kLong, count, state);
+    else TORCH_CHECK(count <= c.batch, "coopsearch: ", count, " entries for a batch of ", c.batch, " envs");
+    if (status.has_value() && status->defined()) check_dev(*status, "status", at::kInt, 4, state);
+    check_outputs(c, state, 1, obs, state_out);
+    ok(cs_restore(&c, state.data_ptr(), records.data_ptr(), n_records, opt_ptr<const int64_t>(src), opt_ptr<const int64_t>(dst), count,
+                  opt_ptr<int32_t>(status), opt_ptr<float>(obs), opt_ptr<float>(state_out), stream_of(state)));
+}
+
 // ---- caller-side rows: agent network forward, fused closed loop, episode assembly ------------
 
 void check_f32(const Tensor &t, const char *name, int64_t numel, const Tensor &like) {
@@ -577,6 +618,10 @@ TORCH_LIBRARY(coopsearch, m) {
     m.def("env_metrics(Tensor cfg, Tensor(a!) state, Tensor(b!) out4) -> ()", &env_metrics);
     m.def("mt_advance(Tensor cfg, Tensor(a!) state, int min_ahead) -> ()", &mt_advance);
     m.def("mt_canonical(Tensor cfg, Tensor state, Tensor(a!) rows_out) -> ()", &mt_canonical);
+    m.def("snapshot_bytes(Tensor cfg) -> int", &snapshot_bytes);
+    m.def("env_snapshot(Tensor cfg, Tensor state, Tensor? envs, Tensor(a!) records) -> ()", &env_snapshot);
+    m.def("env_restore(Tensor cfg, Tensor(a!) state, Tensor records, Tensor? src, Tensor? dst, Tensor(b!)? status, Tensor(c!)? obs, "
+          "Tensor(d!)? state_out) -> ()", &env_restore);
     m.def("policy_packed_floats() -> int", &policy_packed_floats);
     m.def("policy_forward(Tensor packed, Tensor obs, int obs_stride, int obs_offset, Tensor? last, Tensor? feat, int rows_per_feat, "
           "Tensor(a!) hidden, Tensor(b!)? q, Tensor(c!) actions, int rows, int n_agents, int n_actions, float epsilon, Tensor? eps_env, "

@@ -419,6 +419,18 @@ class BatchedFlightEnv:
         """Re-emit get_obs()/get_state() from the device state (after editing raw())."""
         self._ops.env_emit(self._cfg_t, self._blob, self._obs, self._state)
 
+    def snapshot(self, envs=None):
+        """The logical state of the envs `envs` (int64 indices; None: all) as an `EnvSnapshot`: one record per env, equal byte
+        for byte for equal states whichever kernels ran (cs_snapshot).  Nothing is changed."""
+        from . import snapshot as _snap
+        return _snap.snapshot(self, envs)
+
+    def restore(self, snap, src=None, dst=None, status=None):
+        """Env dst[i] takes record src[i] of `snap` (None: i; src may repeat: a fork), see snapshot.restore (cs_restore).  This
+        -- not copying through raw() -- is how an env's state is set."""
+        from . import snapshot as _snap
+        _snap.restore(self, snap, src, dst, status)
+
     def get_obs(self):
         """[B, n, 4] (flight: [B, n, map*map + 4], map first) float32 -- live buffer."""
         return self._obs
@@ -606,6 +618,14 @@ class _SingleEnvAdapter:
     def render(self):
         """flight_env_easy.py:324-343: the reference's interactive scatter (plt.draw + plt.pause) of this env."""
         self._env.render(0)
+
+    def snapshot(self):
+        """This env's state as a one-record `EnvSnapshot` (BatchedFlightEnv.snapshot)."""
+        return self._env.snapshot()
+
+    def restore(self, snap, src=None):
+        """Take record `src` (default 0) of `snap`, e.g. one env captured from a batch (BatchedFlightEnv.restore)."""
+        self._env.restore(snap, src=[0 if src is None else int(src)], dst=[0])
 
     def close(self):
         pass

@@ -87,6 +87,28 @@ class _EpisodeRing:
     def can_sample(self, batch_size):
         return self.current_size >= batch_size
 
+    def state_dict(self, with_buffer=True):
+        """The cursor and the FILLED part of every buffer, on the host (with_buffer=False: an empty ring, cursor at 0)."""
+        if not with_buffer:
+            return {"current_idx": 0, "current_size": 0, "buffers": {k: v[:0].cpu() for k, v in self.buffers.items()}}
+        return {"current_idx": int(self.current_idx), "current_size": int(self.current_size),
+                "buffers": {k: v[:self.current_size].cpu() for k, v in self.buffers.items()}}
+
+    def check_state_dict(self, sd):
+        n = int(sd["current_size"])
+        if tuple(sd["buffers"]) != tuple(self.keys) or n > self.size:
+            raise ValueError(f"ring state with keys {tuple(sd['buffers'])} and {n} episodes for a ring of {self.keys}, size {self.size}")
+        for k, v in sd["buffers"].items():
+            if tuple(v.shape) != (n,) + tuple(self.buffers[k].shape[1:]):
+                raise ValueError(f"ring state: {k} is {tuple(v.shape)}, the ring's episodes are {tuple(self.buffers[k].shape[1:])}")
+
+    def load_state_dict(self, sd):
+        self.check_state_dict(sd)
+        n = int(sd["current_size"])
+        for k, v in sd["buffers"].items():
+            self.buffers[k][:n].copy_(v)
+        self.current_idx, self.current_size = int(sd["current_idx"]), n
+
     def sample(self, batch_size, generator=None):
         """Uniform with replacement over the filled part (replay_buffer.py:63-68), drawn on the device."""
         idx = torch.randint(0, self.current_size, (batch_size,), device=self.device, generator=generator)

@@ -48,8 +48,42 @@ def get_model_idx(model_dir):
         return 0
     idx = 0
     for name in os.listdir(model_dir):
-        idx = max(idx, int(name.split("_")[0]))
+        lead = name.split("_")[0]
+        if lead.isdigit():   # (the run's state file, STATE_FILE, lives here too: it is no checkpoint)
+            idx = max(idx, int(lead))
     return idx + 1
+
+
+STATE_FILE = "state.pt"   # <model_path>/state.pt: Runner.save_state's file for args.state_cycle / args.load_state
+STATE_FORMAT = 1
+
+
+def learner_state(learner):
+    """Every network of a learner (targets included) and every optimizer, by attribute name."""
+    return {"modules": {k: v.state_dict() for k, v in vars(learner).items() if isinstance(v, torch.nn.Module)},
+            "optimizers": {k: v.state_dict() for k, v in vars(learner).items() if isinstance(v, torch.optim.Optimizer)}}
+
+
+def check_learner_state(learner, sd):
+    """ValueError unless `sd` names this learner's networks and optimizers, with every tensor of a network in its shape."""
+    have = learner_state(learner)
+    for kind in ("modules", "optimizers"):
+        if sorted(sd[kind]) != sorted(have[kind]):
+            raise ValueError(f"learner state: {kind} {sorted(sd[kind])} do not match this learner's {sorted(have[kind])}")
+    for name, msd in sd["modules"].items():
+        mine = have["modules"][name]
+        if sorted(msd) != sorted(mine) or any(tuple(msd[k].shape) != tuple(mine[k].shape) for k in mine):
+            raise ValueError(f"learner state: the tensors of {name} do not match this learner's")
+    for name, osd in sd["optimizers"].items():
+        if [len(g["params"]) for g in osd["param_groups"]] != [len(g["params"]) for g in have["optimizers"][name]["param_groups"]]:
+            raise ValueError(f"learner state: the parameter groups of {name} do not match this learner's")
+
+
+def load_learner_state(learner, sd):
+    check_learner_state(learner, sd)
+    for kind in ("modules", "optimizers"):
+        for k, v in sd[kind].items():
+            getattr(learner, k).load_state_dict(v)
 
 
 def apply_run_defaults(args):
@@ -65,7 +99,10 @@ class Runner:
     get_reinforce_args and apply_env_info; args.alg selects the learner.  The parts (learner, agents, schedule, collector,
     buffer) are built here unless passed in.  args.compact_episodes (flight only; default False): episodes are collected,
     stored and learnt from in the map-once format (replay.COMPACT_KEYS) -- a CompactReplayBuffer and
-    generate_episodes(compact=True); the schedule of calls is the same.  args.conv_impl (absent: "torch") goes to the learner."""
+    generate_episodes(compact=True); the schedule of calls is the same.  args.conv_impl (absent: "torch") goes to the learner.
+    Exact resume (DESIGN.md section 14): `save_state` / `load_state` carry everything that changes during `run`;
+    args.state_cycle (absent or 0: never) writes <model_path>/state.pt every that many epochs, args.load_state=True loads it
+    here.  `epoch` and `train_steps` count what this run has done; `run` goes on from them."""
 
     def __init__(self, env, args, learner=None, agents=None, schedule=None, collector=None, buffer=None):
         alg = getattr(args, "alg", None)
@@ -101,21 +138,90 @@ class Runner:
         self.result_path = args.result_dir + run_name(args)
         os.makedirs(self.result_path, exist_ok=True)   # runner.py:33-39
         os.makedirs(self.model_path, exist_ok=True)
+        self.epoch, self.train_steps = 0, 0
+        self.state_path = os.path.join(self.model_path, STATE_FILE)
+        if getattr(args, "load_state", False):
+            if not os.path.exists(self.state_path):
+                raise Exception("No state!")
+            self.load_state(self.state_path)
 
     def run(self, num, n_epoch=None):
-        """runner.py:41-84 for n_epoch epochs (default args.n_epoch); results are saved after every evaluation and at the end."""
+        """runner.py:41-84 up to epoch n_epoch (default args.n_epoch), starting at self.epoch (0 unless a state was loaded or an
+        earlier call ran); results are saved after every evaluation and at the end."""
         a = self.args
         n_epoch = a.n_epoch if n_epoch is None else int(n_epoch)
-        train_steps = 0
-        for epoch in range(n_epoch):
+        state_cycle = int(getattr(a, "state_cycle", 0) or 0)
+        for epoch in range(self.epoch, n_epoch):
             if epoch % a.evaluate_cycle == 0:
                 win_rate, episode_reward, targets_find = self.evaluate()
                 self.win_rates.append(win_rate)
                 self.targets_find.append(targets_find)
                 self.episode_rewards.append(episode_reward)
                 self.save_results(num)
-            train_steps = self.train_epoch(train_steps)
+            self.train_steps = self.train_epoch(self.train_steps)
+            self.epoch = epoch + 1
+            if state_cycle and self.epoch % state_cycle == 0:
+                self.save_state(self.state_path)
         self.save_results(num)
+
+    def _rng_device(self):
+        dev = torch.device(getattr(self.env, "device", "cpu"))
+        return dev if dev.type == "cuda" else None
+
+    def save_state(self, path, with_buffer=True):
+        """Everything that changes during `run`, in one file: the env snapshot, every learner network (targets included) and
+        optimizer, the ring (its filled part; with_buffer=False: an empty ring), every env's epsilon, the acting agents' noise
+        counter / hidden state / last actions, torch's CPU and device generator states, epoch, train_steps and the result lists.
+        Written through a temporary file and a rename: a reader sees the old file or the new one.  Synchronises."""
+        dev = self._rng_device()
+        state = {"format": STATE_FORMAT, "alg": self.args.alg, "epoch": int(self.epoch), "train_steps": int(self.train_steps),
+                 "env": self.env.snapshot().cpu().state_dict(),
+                 "learner": learner_state(self.learner),
+                 "buffer": None if self.buffer is None else self.buffer.state_dict(with_buffer=with_buffer),
+                 "schedule": self.schedule.state_dict(), "agents": self.agents.state_dict(),
+                 "rng": {"cpu": torch.get_rng_state(), "device": None if dev is None else torch.cuda.get_rng_state(dev)},
+                 "results": {"win_rates": [float(v) for v in self.win_rates], "targets_find": [float(v) for v in self.targets_find],
+                             "episode_rewards": [float(v) for v in self.episode_rewards]}}
+        tmp = path + ".tmp"
+        torch.save(state, tmp)
+        os.replace(tmp, path)
+
+    def load_state(self, path):
+        """The inverse of save_state, into this Runner's parts (built for the same args and batch): afterwards `run` continues
+        exactly as the saved run would have.  The env's seeds do not matter: every env takes its record.  A file that does not
+        fit (other alg, batch, team, ring or network shapes) raises ValueError before anything is changed."""
+        from .snapshot import EnvSnapshot, env_meta
+        state = torch.load(path, map_location="cpu", weights_only=True)
+        if state.get("format") != STATE_FORMAT or state.get("alg") != self.args.alg:
+            raise ValueError(f"{path}: state of format {state.get('format')!r} for alg {state.get('alg')!r}; this Runner reads "
+                             f"format {STATE_FORMAT} and trains {self.args.alg!r}")
+        snap = EnvSnapshot.from_state_dict(state["env"])
+        if len(snap) != self.env.batch:
+            raise ValueError(f"{path}: {len(snap)} env records for a batch of {self.env.batch}")
+        if (state["buffer"] is None) != (self.buffer is None):
+            raise ValueError(f"{path}: the saved run and this one disagree on having a replay ring")
+        # every part is validated before any part is touched: a refused file leaves this Runner as it was
+        snap.check(env_meta(self.env))
+        check_learner_state(self.learner, state["learner"])
+        if self.buffer is not None:
+            self.buffer.check_state_dict(state["buffer"])
+        self.schedule.check_state_dict(state["schedule"])
+        self.agents.check_state_dict(state["agents"])
+        self.env.restore(snap)
+        load_learner_state(self.learner, state["learner"])
+        if self.buffer is not None:
+            self.buffer.load_state_dict(state["buffer"])
+        self.schedule.load_state_dict(state["schedule"])
+        self.agents.load_state_dict(state["agents"])
+        self.agents.sync_weights()   # the acting blob follows the loaded network
+        self.epoch, self.train_steps = int(state["epoch"]), int(state["train_steps"])
+        res = state["results"]
+        self.win_rates, self.targets_find = list(res["win_rates"]), list(res["targets_find"])
+        self.episode_rewards = list(res["episode_rewards"])
+        torch.set_rng_state(state["rng"]["cpu"])
+        dev = self._rng_device()
+        if dev is not None and state["rng"]["device"] is not None:
+            torch.cuda.set_rng_state(state["rng"]["device"], dev)
 
     def train_epoch(self, train_steps):
         """Collect, store, learn, repack: one epoch without its evaluation.  Returns the updated learn-call count."""

@@ -38,8 +38,8 @@ extern "C" {
                               cs_epsilon_step, CS_KERNEL_LANEV; 7: CS_CHECK_ACTIONS, cs_has_legacy_kernels;
                               still 7: cs_gru_seq_forward, cs_gru_seq_backward, cs_learn_last_error were ADDED, then
                               cs_episode_returns, then cs_policy_pack_device, then cs_collect_flight, cs_compact_out and
-                              cs_store_episodes_compact (no existing export or struct changed: a version-7 caller works
-                              unchanged) */
+                              cs_store_episodes_compact, then cs_snapshot_bytes, cs_snapshot and cs_restore (no existing export
+                              or struct changed: a version-7 caller works unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
 #define CS_MAX_MAP 64
@@ -240,6 +240,47 @@ int cs_mt_canonical(const cs_config *cfg, void *state_dev, uint32_t *rows_out_de
 
 /* get_obs() + get_state() of every env without stepping. */
 int cs_emit(const cs_config *cfg, void *state_dev, float *obs_dev, float *state_out_dev, void *stream);
+
+/* ---- env snapshot / restore -------------------------------------------------------------------------------------
+ * An env's LOGICAL state as one fixed-size record, and back.  The state blob itself is not such a thing: its MT19937 row is
+ * stored in a form that depends on which kernel ran last (cs_layout.ahead_off), words 624..655 mirror words 0..31, the hit
+ * tape (cs_layout.tape_off) is accepted by threshold and word count alone, and CS_H_FLAGS bits 1-2 and the job records are
+ * leftovers of the last launch.  Copying one env's arrays over another's is therefore wrong; these two calls are the way.
+ * Two envs in the same logical state give byte-equal records, whichever kernels brought them there.
+ *
+ * Record (cs_snapshot_bytes(cfg) bytes, a multiple of 16; CS_SNAPSHOT_VERSION 1):
+ *      0  uint32 [16]     0x50534343, format version, variant, n_agents, n_targets, map_size, 0 ...
+ *     64  uint32 [16]     the env's CS_H_* words with CS_H_FLAGS bits 1-2 clear (words 12..15 zero)
+ *    128  double [16][2]  targets (x, y); rows >= n_targets zero
+ *    384  double [8][4]   agents (x, y, yaw, 0); rows >= n_agents zero
+ *    640  uint32 [624]    the MT19937 row in cs_mt_canonical's form; its cursor is CS_H_MT_POS above
+ *   3136  float [map_size^2]  flight only: the probability map
+ * so cs_snapshot_bytes = 3136 for flight_easy and 3136 + 4 map_size^2 for flight.  A record is per env: it can go to an env
+ * of any batch size or shard whose variant, n_agents, n_targets and map_size are the record's.  Everything else lives in
+ * cs_config, not in the record, and belongs to the RESTORING env: time_limit, detect_prob, view_range, velocity, safe_dist,
+ * the force constants, agent_mode, target_mode and the target file.
+ *
+ * Both calls enqueue on `stream` and never synchronise; records_dev must be 16-byte aligned (CS_E_ARG otherwise). */
+#define CS_SNAPSHOT_VERSION 1
+/* Host only; 0 for a config that cs_state_layout refuses. */
+size_t cs_snapshot_bytes(const cs_config *cfg);
+/* Record i (at records_dev + i * cs_snapshot_bytes) = env env_idx_dev[i] (int64 [count]; NULL: env i, count <= batch).  The
+ * state is only read.  An index outside 0..batch-1 gives an all-zero record, which cs_restore refuses. */
+int cs_snapshot(const cs_config *cfg, const void *state_dev, const int64_t *env_idx_dev, int64_t count, void *records_dev,
+                void *stream);
+/* Env dst_idx_dev[i] takes record src_idx_dev[i] of the n_records at records_dev, for i < count (int64 [count] each; NULL: i).
+ * src may repeat (one state forked into many envs); the dst entries must be distinct, as cs_store_episodes' slots.  A
+ * restored env holds the record's header words, targets, agents and map, its row in canonical form with the mirror words
+ * rebuilt and ahead = 624, a hit tape rebuilt from THAT row (no tape of the env's previous stream survives), and nothing
+ * pending for the map sweep.  Envs not named in dst are untouched, bit for bit.  An entry whose record header does not match
+ * cfg (its 16 identification words; also a cursor word that is not an even value below 624, or a nonzero header word 12..15),
+ * or whose src / dst index is out of range, leaves its env untouched -- that is all a record is checked for: the remaining
+ * CS_H_* words, targets, agents, row and map ARE the state and are taken as they are, so records come from cs_snapshot.
+ * status_dev (int32 [4], may be NULL) names the FIRST refused entry: {1, kind, i, value} with kind 1 = src out of range, 2 = dst out of range (value: the index), 3 = record refused (value: the first offending uint32 word of the
+ * record); {0, -1, -1, 0} when every entry was applied.  obs_dev / state_out_dev as in cs_reset: get_obs() / get_state() of
+ * ALL envs afterwards, either may be NULL. */
+int cs_restore(const cs_config *cfg, void *state_dev, const void *records_dev, int64_t n_records, const int64_t *src_idx_dev,
+               const int64_t *dst_idx_dev, int64_t count, int32_t *status_dev, float *obs_dev, float *state_out_dev, void *stream);
 
 /* Per-device partial sums of the evaluation metrics of runner.py:86-96 / rollout.py:190-198:
  * out4_dev[0] += sum total_reward, [1] += sum win_flag, [2] += sum target_find, [3] += number of envs.
