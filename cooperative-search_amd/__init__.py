@@ -17,6 +17,7 @@ from .learner import GRUSequence, MixerNet, QMixLearner, get_mixer_args, unroll_
 from .learner import DOPLearner, OffPGCritic, ReinforceLearner, get_dop_args, get_reinforce_args  # noqa: F401
 from .runner import Runner, get_model_idx, run_name  # noqa: F401
 from .snapshot import EnvSnapshot  # noqa: F401
+from .render import RenderSpec, episode_tables, render_episodes, render_episodes_torch, write_frames  # noqa: F401
 
 __all__ = ["BatchedFlightEnv", "FlightSearchEnvEasy", "FlightSearchEnv", "load_targets", "default_circle_dict",
            "get_flight_easy_args", "get_flight_args", "make_env_args", "lib"]

@@ -256,6 +256,10 @@ class EpisodeCollector:
         """`evaluate` (below) on this collector's env: Runner.evaluate's (win_rate, episode_reward, targets_find)."""
         return evaluate(self.env, policy, batches)
 
+    def collect_experiment_data(self, policy, batches=1, num=None, result_path=None, return_stats=False):
+        """`collect_experiment_data` (below) on this collector's env."""
+        return collect_experiment_data(self.env, policy, batches, num=num, result_path=result_path, return_stats=return_stats)
+
 
 def _run_episodes(env, policy, init):
     """One batch of episodes with frozen termination; yields (t, target_find) after every step."""

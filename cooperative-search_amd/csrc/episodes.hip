@@ -151,6 +151,8 @@ __global__ __launch_bounds__(256) void k_compact_small(CompactParams p) {
     for (int a = 0; a < p.n; a++) p.out.u[e * p.n + a] = real ? (float)(int)p.u_tab[((size_t)t * p.B + b) * p.n + a] : 0.0f;
 }
 
+#include "render.h"   // k_render_episodes: episode rows -> RGB frames (cs_render_episodes)
+
 thread_local char g_eerr[160] = "";
 
 }  // namespace
@@ -210,6 +212,40 @@ int cs_store_episodes_compact(int B, int T, int n_agents, int cells, int state_w
     hipLaunchKernelGGL(k_compact_small, dim3((unsigned)(((size_t)B * T + 255) / 256)), dim3(256), 0, s, p);
     if (hipGetLastError() != hipSuccess) {
         snprintf(g_eerr, sizeof(g_eerr), "cs_store_episodes_compact: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    return CS_OK;
+}
+
+int cs_render_episodes(const cs_render_params *p, const float *states_dev, const float *maps_dev, const int32_t *counts_dev,
+                       int E, int R, uint8_t *frames_dev, void *stream) {
+    const char *bad = nullptr;
+    if (!p || !states_dev || !counts_dev || !frames_dev || !p->palette_dev || !p->lut_dev) bad = "a NULL pointer";
+    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
+    else if (p->n_targets < 1 || p->n_targets > CS_MAX_TARGETS) bad = "n_targets must be 1..16";
+    else if (p->state_width != 4 * p->n_agents + 3 * p->n_targets) bad = "state_width must be 4 n_agents + 3 n_targets";
+    else if (p->size < 16 || p->size > 1024 || p->size % 4 != 0) bad = "size must be a multiple of 4 in 16..1024";
+    else if (E < 1 || E > 65535 || R < 1) bad = "E must be 1..65535 and R >= 1";
+    else if (p->rv < 0 || p->rv > 32767 || p->rt < 0 || p->rt > 32767 || p->rtr < 0 || p->rtr > 32767 || p->tri_len < 0 ||
+             p->tri_len > 16383)
+        bad = "a radius is out of range (rv, rt, rtr 0..32767, tri_len 0..16383)";
+    else if ((uintptr_t)frames_dev % 4 != 0) bad = "frames_dev must be 4-byte aligned";
+    else if (maps_dev && (p->side < 1 || p->side > CS_MAX_MAP || p->map_width != p->side * p->side))
+        bad = "side must be 1..64 and map_width side * side";
+    if (bad) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_render_episodes: %s", bad);
+        return CS_E_CONFIG;
+    }
+    auto rgb = [](const uint8_t *c) { return (unsigned)c[0] | ((unsigned)c[1] << 8) | ((unsigned)c[2] << 16); };
+    const RenderArgs a{states_dev, maps_dev, counts_dev, frames_dev, p->palette_dev, p->lut_dev, R, p->state_width, p->n_agents,
+                       p->n_targets, p->size, maps_dev ? p->side : 0, maps_dev ? p->map_width : 0, p->rv, p->rt, p->rtr, p->tri_len,
+                       p->layers, rgb(p->background), rgb(p->sensor_tint), rgb(p->sensor_ring), rgb(p->target), rgb(p->target_found),
+                       rgb(p->bar_on), rgb(p->bar_off)};
+    const int quads = p->size * p->size / 4;
+    hipLaunchKernelGGL(k_render_episodes, dim3((quads + RENDER_THREADS - 1) / RENDER_THREADS, E), dim3(RENDER_THREADS), 0,
+                       (hipStream_t)stream, a);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_render_episodes: kernel launch failed");
         return CS_E_LAUNCH;
     }
     return CS_OK;

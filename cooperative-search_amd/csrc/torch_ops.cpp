@@ -550,6 +550,64 @@ void store_episodes_compact(const Tensor &map_tab, const Tensor &s_tab, const Te
     TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
 }
 
+// ---- episode frames (cs_render_episodes): states [E, R, 4n + 3m], maps [E, R, side^2] or None, counts int32 [E] -> frames uint8
+// [E, R, W, W, 3].  radii = (rv, rt, rtr, tri_len), colours = 7 x (r, g, b): background, sensor tint, sensor ring, target, found
+// target, bar on, bar off.  What the shapes and integers say is checked first (nothing is dereferenced), then the tensors.
+void render_episodes(const Tensor &states, const c10::optional<Tensor> &maps, const Tensor &counts, int64_t n_agents,
+                     int64_t n_targets, int64_t side, int64_t size, std::vector<int64_t> radii, int64_t layers,
+                     std::vector<int64_t> colours, const Tensor &palette, const Tensor &lut, Tensor frames) {
+    const bool has_maps = maps.has_value() && maps->defined();
+    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: render_episodes: n_agents must be 1..8, got ", n_agents);
+    TORCH_CHECK(n_targets >= 1 && n_targets <= CS_MAX_TARGETS, "coopsearch: render_episodes: n_targets must be 1..16, got ", n_targets);
+    TORCH_CHECK(size >= 16 && size <= 1024 && size % 4 == 0, "coopsearch: render_episodes: size must be a multiple of 4 in 16..1024, got ",
+                size);
+    const int64_t S = 4 * n_agents + 3 * n_targets;
+    TORCH_CHECK(states.dim() == 3 && states.size(2) == S, "coopsearch: render_episodes: states must be [E, R, ", S, "]");
+    const int64_t E = states.size(0), R = states.size(1);
+    TORCH_CHECK(E >= 1 && E <= 65535, "coopsearch: render_episodes: E must be 1..65535, got ", E);
+    TORCH_CHECK(R >= 1, "coopsearch: render_episodes: R must be >= 1");
+    if (has_maps)
+        TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP && maps->dim() == 3 && maps->size(0) == E && maps->size(1) == R &&
+                        maps->size(2) == side * side,
+                    "coopsearch: render_episodes: maps must be [E, R, side * side] with side 1..", CS_MAX_MAP, " (side ", side, ")");
+    TORCH_CHECK(radii.size() == 4 && radii[0] >= 0 && radii[0] <= 32767 && radii[1] >= 0 && radii[1] <= 32767 && radii[2] >= 0 &&
+                    radii[2] <= 32767 && radii[3] >= 0 && radii[3] <= 16383,
+                "coopsearch: render_episodes: radii must be (rv, rt, rtr 0..32767, tri_len 0..16383)");
+    TORCH_CHECK(colours.size() == 21, "coopsearch: render_episodes: colours must be 7 x (r, g, b)");
+    for (int64_t c : colours) TORCH_CHECK(c >= 0 && c <= 255, "coopsearch: render_episodes: a colour channel is outside 0..255");
+    TORCH_CHECK(layers >= 0 && layers < 64, "coopsearch: render_episodes: layers must be CS_RENDER_* bits");
+    TORCH_CHECK(states.is_cuda(), "coopsearch: render_episodes: states must be a GPU tensor");
+    check_f32(states, "states", E * R * S, states);
+    if (has_maps) check_f32(*maps, "maps", E * R * side * side, states);
+    check_dev(counts, "counts", at::kInt, E, states);
+    check_dev(palette, "palette", at::kByte, CS_MAX_AGENTS * 3, states);
+    check_dev(lut, "lut", at::kByte, 256 * 3, states);
+    TORCH_CHECK(frames.dim() == 5 && frames.size(0) == E && frames.size(1) == R && frames.size(2) == size && frames.size(3) == size &&
+                    frames.size(4) == 3,
+                "coopsearch: render_episodes: frames must be [", E, ", ", R, ", ", size, ", ", size, ", 3]");
+    check_dev(frames, "frames", at::kByte, E * R * size * size * 3, states);
+    cs_render_params p{};
+    p.n_agents = (int32_t)n_agents;
+    p.n_targets = (int32_t)n_targets;
+    p.state_width = (int32_t)S;
+    p.size = (int32_t)size;
+    p.side = has_maps ? (int32_t)side : 0;
+    p.map_width = has_maps ? (int32_t)(side * side) : 0;
+    p.rv = (int32_t)radii[0];
+    p.rt = (int32_t)radii[1];
+    p.rtr = (int32_t)radii[2];
+    p.tri_len = (int32_t)radii[3];
+    p.layers = (int32_t)layers;
+    uint8_t *dst[7] = {p.background, p.sensor_tint, p.sensor_ring, p.target, p.target_found, p.bar_on, p.bar_off};
+    for (int k = 0; k < 7; k++)
+        for (int ch = 0; ch < 3; ch++) dst[k][ch] = (uint8_t)colours[3 * k + ch];
+    p.palette_dev = palette.data_ptr<uint8_t>();
+    p.lut_dev = lut.data_ptr<uint8_t>();
+    const int rc = cs_render_episodes(&p, states.data_ptr<float>(), opt_ptr<const float>(maps), counts.data_ptr<int32_t>(), (int)E,
+                                      (int)R, frames.data_ptr<uint8_t>(), stream_of(states));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
 int64_t abi_version() { return cs_abi_version(); }
 
 // ---- QMIX learner: the GRU recurrence over T steps (cs_gru_seq_forward / cs_gru_seq_backward) ------------------------------
@@ -654,6 +712,8 @@ TORCH_LIBRARY(coopsearch, m) {
           "Tensor(g!) map_tab, Tensor(h!) state_tab) -> ()", &collect_flight);
     m.def("store_episodes_compact(Tensor map_tab, Tensor s_tab, Tensor u_tab, Tensor r_tab, Tensor term_tab, Tensor? slots, "
           "Tensor(a!)[] outs) -> ()", &store_episodes_compact);
+    m.def("render_episodes(Tensor states, Tensor? maps, Tensor counts, int n_agents, int n_targets, int side, int size, int[] radii, "
+          "int layers, int[] colours, Tensor palette, Tensor lut, Tensor(a!) frames) -> ()", &render_episodes);
     m.def("gru_seq_forward(Tensor w_hh, Tensor b_hh, Tensor gi, Tensor? h0, int T, int rows, Tensor(a!) h_out, "
           "Tensor(b!)? saved_out) -> ()", &gru_seq_forward);
     m.def("gru_seq_backward(Tensor w_hh, Tensor dh_seq, Tensor h_seq, Tensor? h0, Tensor saved, int T, int rows, "

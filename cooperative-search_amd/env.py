@@ -486,6 +486,26 @@ class BatchedFlightEnv:
                         raw["agent"][b, :self.n_agents, :2].cpu().numpy(), int(hdr[_lib.H_TARGET_FIND]), self.target_num,
                         self.map_size, path=path, pause=pause)
 
+    def render_frames(self, envs=None, size=256, spec=None):
+        """uint8 [K, W, W, 3] on the device: one picture per chosen env (int64 indices; None: all) of the CURRENT get_state()
+        -- and the current probability map on flight -- drawn by the frame kernel (render.render_episodes: headings, sensor
+        discs, found targets, progress bar; one row per env, so no trail).  spec: a `render.RenderSpec` (default: this env's
+        team and sensor at `size` pixels).  `render()` stays the reference's host-side scatter."""
+        import dataclasses
+
+        from . import render as _render
+        spec = _render.RenderSpec.for_env(self, size) if spec is None else spec
+        spec = dataclasses.replace(spec, trail=False)
+        states, maps = self.get_state(), self.raw()["prob"].reshape(self.batch, self.cells) if self.flight else None
+        if envs is not None:
+            idx = torch.as_tensor(envs, device=self.device).to(torch.int64).reshape(-1)
+            states, maps = states.index_select(0, idx), None if maps is None else maps.index_select(0, idx)
+        K = int(states.shape[0])
+        counts = torch.ones(K, dtype=torch.int32, device=self.device)
+        frames = _render.render_episodes(states.reshape(K, 1, -1).contiguous(), None if maps is None else maps.reshape(K, 1, -1).contiguous(),
+                                         counts, spec)
+        return frames[:, 0]
+
     def close(self):
         pass
 
@@ -618,6 +638,10 @@ class _SingleEnvAdapter:
     def render(self):
         """flight_env_easy.py:324-343: the reference's interactive scatter (plt.draw + plt.pause) of this env."""
         self._env.render(0)
+
+    def render_frame(self, size=256, spec=None):
+        """This env's current picture as a uint8 [W, W, 3] ndarray (BatchedFlightEnv.render_frames)."""
+        return self._env.render_frames(size=size, spec=spec)[0].cpu().numpy()
 
     def snapshot(self):
         """This env's state as a one-record `EnvSnapshot` (BatchedFlightEnv.snapshot)."""

@@ -14,6 +14,7 @@ reference's makes them on its n_episodes; an evaluation covers ceil(evaluate_epo
 episodes.  DOP and REINFORCE take the epsilon of env 0 (`schedule.values[0]`): the reference has one RolloutWorker and one
 epsilon, a batch of B envs carries B of them (collector.EpsilonSchedule), and env 0 anneals exactly as that one worker would.
 """
+import errno
 import math
 import os
 
@@ -258,6 +259,52 @@ class Runner:
         self.agents.check_weights()
         batches = max(1, math.ceil(self.args.evaluate_epoch / self.env.batch))
         return self.collector.evaluate(self.agents.policy(0.0, True), batches)
+
+    def load_checkpoint(self, num):
+        """runner.py:118-134 / :142-154: checkpoint `num` of this run's model directory into the learner (the files of
+        _RESUME[alg]; a missing one is the FileNotFoundError torch.load raises there), then the acting network follows."""
+        files = [os.path.join(self.model_path, f"{num}_{part}_net_params.pkl") for part in _RESUME[self.args.alg]]
+        for f in files:
+            if not os.path.exists(f):
+                raise FileNotFoundError(errno.ENOENT, os.strerror(errno.ENOENT), f)
+        self.learner.load_model(*files)
+        self.agents.sync_weights()
+        self.agents.check_weights()
+
+    def replay(self, num, episodes=None, size=256, path=None):
+        """runner.py:118-137 with pictures: load checkpoint `num`, run ONE greedy batch from reset(init=True)
+        (generate_replay's reset, rollout.py:145) and draw its first `episodes` envs (default min(batch, 16)) as `size` x `size`
+        frames on the device (render.render_episodes: one launch for every step of every episode).  Writes
+        <result_path>/replay_<num>.gif (`path` overrides; the array as .npy where PIL is missing), prints the reference's line
+        for env 0 and returns (frames uint8 [K, T + 1, W, W, 3], targets_find [B], episode_reward [B], steps [B]) as device
+        tensors."""
+        from . import render as _render
+        self.load_checkpoint(num)
+        batch, episode_reward, _win, targets_find = self.collector.generate_episodes(agents=self.agents, evaluate=True, init=True,
+                                                                                     **self._collect_kw)
+        states, maps, counts = _render.episode_tables(batch, self.args)
+        K = min(int(states.shape[0]), 16 if episodes is None else max(1, int(episodes)))
+        spec = _render.RenderSpec.for_env(self.args, size)
+        frames = _render.render_episodes(states[:K].contiguous(), None if maps is None else maps[:K].contiguous(),
+                                         counts[:K].contiguous(), spec)
+        written = _render.write_frames(frames, path if path is not None else os.path.join(self.result_path, f"replay_{num}.gif"))
+        print("targets_find: ", int(targets_find[0]), " reward: ", int(episode_reward[0]))   # runner.py:137
+        print("replay saved:", written)
+        return frames, targets_find, episode_reward, counts.to(torch.int64) - 1
+
+    def collect_experiment_data(self, num, replay_times):
+        """runner.py:139-172: load checkpoint `num`, run at least `replay_times` greedy episodes from reset(init=True) --
+        ceil(replay_times / B) batches -- and save the percentage of targets found by every step as
+        <result_path>/average_res_<num>.npy.  Prints the reference's two lines; returns (curve, stats)."""
+        self.load_checkpoint(num)
+        batches = max(1, math.ceil(int(replay_times) / self.env.batch))
+        res, stats = self.collector.collect_experiment_data(self.agents.policy(0.0, True), batches, num=num,
+                                                            result_path=self.result_path, return_stats=True)
+        print(stats["targets_find"], stats["episode_reward"], stats["steps"])
+        idx = [i for i in (10, 20, 40, 60, 80, 100, 150, 199) if i < len(res)]
+        print(np.asarray(res)[idx])
+        print("process data saved!")
+        return res, stats
 
     def save_results(self, num):
         """runner.py:98-116: targets_find_<num>.npy (search envs) and episode_rewards_<num>.npy; plt_<num>.png when matplotlib

@@ -38,8 +38,8 @@ extern "C" {
                               cs_epsilon_step, CS_KERNEL_LANEV; 7: CS_CHECK_ACTIONS, cs_has_legacy_kernels;
                               still 7: cs_gru_seq_forward, cs_gru_seq_backward, cs_learn_last_error were ADDED, then
                               cs_episode_returns, then cs_policy_pack_device, then cs_collect_flight, cs_compact_out and
-                              cs_store_episodes_compact, then cs_snapshot_bytes, cs_snapshot and cs_restore (no existing export
-                              or struct changed: a version-7 caller works unchanged) */
+                              cs_store_episodes_compact, then cs_snapshot_bytes, cs_snapshot and cs_restore, then cs_render_params and
+                              cs_render_episodes (no existing export or struct changed: a version-7 caller works unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
 #define CS_MAX_MAP 64
@@ -448,6 +448,47 @@ int cs_store_episodes_compact(int B, int T, int n_agents, int cells, int state_w
                               const float *s_tab_dev, const int64_t *u_tab_dev, const float *r_tab_dev,
                               const uint8_t *term_tab_dev, const int64_t *slot_dev, const cs_compact_out *out, void *stream);
 const char *cs_episodes_last_error(void);
+
+/* ---- episode frames: the state (and map) rows of E episodes -> RGB pictures -----------------
+ * The reference's only picture is env.render(), a matplotlib scatter of one instant (flight_env_easy.py:324-343).  This
+ * call draws EVERY row of E recorded episodes as a size x size RGB frame in one launch: the flight map as a heat layer,
+ * every agent's sensor disc, the path it has flown so far, the targets (found ones in another colour), the agents as
+ * triangles pointing along their heading, and a progress bar of found targets.  The frame is DEFINED by
+ * render.render_episodes_torch (stock torch ops, integer geometry after one quantisation); the kernel reproduces it byte
+ * for byte.
+ *   states_dev  float [E][R][4n + 3m]  get_state() rows: agent i = (xn, yn, cos, sin) at 4i, target j = (xn, yn, found) at 4n + 3j
+ *   maps_dev    float [E][R][side^2]   the flight map of every row, row-major [ix * side + iy]; NULL: no heat layer
+ *   counts_dev  int32 [E]              real rows of episode e: frame t is drawn from row min(t, clamp(counts[e], 1, R) - 1);
+ *                                      rows past the count are never read
+ *   frames_dev  uint8 [E][R][size][size][3], 4-byte aligned; every byte is written (no clearing needed)
+ * With U = 16 * size sub-units across the map, the radii below are in sub-units (render.RenderSpec computes them). */
+enum {
+    CS_RENDER_HEAT = 1, CS_RENDER_SENSOR = 2, CS_RENDER_TRAIL = 4, CS_RENDER_TARGETS = 8, CS_RENDER_AGENTS = 16, CS_RENDER_BAR = 32
+};
+typedef struct cs_render_params {
+    int32_t n_agents;     /* 1..8 */
+    int32_t n_targets;    /* 1..16 */
+    int32_t state_width;  /* floats per state row: 4 n_agents + 3 n_targets */
+    int32_t size;         /* W: frame width and height in pixels, a multiple of 4 in 16..1024 */
+    int32_t side;         /* cells per map side, 1..CS_MAX_MAP (looked at only with maps_dev) */
+    int32_t map_width;    /* floats per map row: side * side (looked at only with maps_dev) */
+    int32_t rv;           /* sensor radius, 0..32767 */
+    int32_t rt;           /* target disc radius, 0..32767 */
+    int32_t rtr;          /* trail radius, 0..32767 */
+    int32_t tri_len;      /* L: an agent's triangle reaches L ahead of its position, L / 2 behind, 0.6 L to each side; 0..16383 */
+    int32_t layers;       /* CS_RENDER_* bits */
+    int32_t reserved;     /* 0 */
+    uint8_t background[4], sensor_tint[4], sensor_ring[4], target[4], target_found[4], bar_on[4], bar_off[4];   /* r, g, b, 0 */
+    const uint8_t *palette_dev;   /* uint8 [8][3]: trail and triangle colour of agent i */
+    const uint8_t *lut_dev;       /* uint8 [256][3]: heat colour of rint(clamp(p, 0, 1) * 255) */
+} cs_render_params;
+
+/* One launch on `stream`, no synchronisation.  CS_E_CONFIG (before any launch) for n_agents outside 1..8, n_targets outside
+ * 1..16, state_width != 4n + 3m, size not a multiple of 4 or outside 16..1024, E < 1, R < 1, a radius out of range, a NULL
+ * pointer (maps_dev alone may be NULL), frames_dev not 4-byte aligned, or, with maps_dev, side outside 1..CS_MAX_MAP or
+ * map_width != side * side.  The message is cs_episodes_last_error()'s. */
+int cs_render_episodes(const cs_render_params *p, const float *states_dev, const float *maps_dev, const int32_t *counts_dev,
+                       int E, int R, uint8_t *frames_dev, void *stream);
 
 /* ---- QMIX learner: the GRU recurrence of the agent network over T steps, forward and backward ---------------------
  * Replaces the per-transition unroll of policy/qmix.py:160-182 (get_q_values) over network/base_net.py:40-46
