@@ -15,6 +15,7 @@ from .agents import AgentRNN, BatchedAgents, FusedAgents, rnn_input_shape  # noq
 from .collector import EpisodeCollector, EpsilonSchedule, evaluate, collect_experiment_data, random_policy  # noqa: F401
 from .learner import GRUSequence, MixerNet, QMixLearner, get_mixer_args, unroll_q  # noqa: F401
 from .learner import DOPLearner, OffPGCritic, ReinforceLearner, get_dop_args, get_reinforce_args  # noqa: F401
+from .learner import PPOLearner, PPOPolicyLoss, ValueCritic, gae, get_ppo_args  # noqa: F401
 from .runner import Runner, get_model_idx, run_name  # noqa: F401
 from .snapshot import EnvSnapshot  # noqa: F401
 from .render import RenderSpec, episode_tables, render_episodes, render_episodes_torch, write_frames  # noqa: F401

@@ -22,7 +22,7 @@ FREEZE_DONE, AUTO_RESET, ACTIONS_I64, KERNEL_GROUP, KERNEL_LANE, KERNEL_SOLO, KE
 EXPORTS = ["cs_abi_version", "cs_source_hash", "cs_has_legacy_kernels", "cs_last_error", "cs_state_layout", "cs_init", "cs_seed", "cs_reset", "cs_step",
            "cs_rollout", "cs_rollout_policy", "cs_rollout_policy_flight", "cs_collect_flight", "cs_emit", "cs_snapshot_bytes", "cs_snapshot", "cs_restore", "cs_metrics", "cs_mt_canonical", "cs_mt_advance", "cs_policy_packed_floats", "cs_policy_pack", "cs_policy_pack_device", "cs_policy_forward",
            "cs_policy_conv_features", "cs_policy_conv_features_backward_scratch", "cs_policy_conv_features_backward", "cs_policy_last_error", "cs_store_episodes", "cs_store_episodes_compact", "cs_render_episodes", "cs_episodes_last_error", "cs_epsilon_step",
-           "cs_gru_seq_forward", "cs_gru_seq_backward", "cs_episode_returns", "cs_learn_last_error"]
+           "cs_gru_seq_forward", "cs_gru_seq_backward", "cs_episode_returns", "cs_gae", "cs_ppo_loss", "cs_learn_last_error"]
 
 
 class CsConfig(C.Structure):
@@ -140,6 +140,8 @@ def load():
     L.cs_gru_seq_forward.argtypes = [vp] * 4 + [C.c_int, C.c_int, vp, vp, vp]
     L.cs_gru_seq_backward.argtypes = [vp] * 5 + [C.c_int, C.c_int, vp, vp, vp, vp]
     L.cs_episode_returns.argtypes = [vp] * 4 + [C.c_int, C.c_int, C.c_float, C.c_float, vp, vp]
+    L.cs_gae.argtypes = [vp] * 5 + [C.c_int, C.c_int, C.c_float, C.c_float, vp, vp, vp]
+    L.cs_ppo_loss.argtypes = [vp] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float] + [vp] * 6 + [C.c_int64, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("cs_abi_version", "cs_source_hash", "cs_has_legacy_kernels", "cs_last_error", "cs_policy_packed_floats", "cs_snapshot_bytes", "cs_policy_last_error",

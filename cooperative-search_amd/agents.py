@@ -113,7 +113,7 @@ class FusedAgents:
 
     def __init__(self, args, batch, device="cuda", net=None, seed=0, env_offset=0):
         """env_offset: global index of this shard's env 0 -- the exploration noise is keyed by the GLOBAL (env, agent)
-        row, so a sharded batch picks the same actions as the whole one.  args.alg == 'reinforce' selects the softmax
+        row, so a sharded batch picks the same actions as the whole one.  args.alg 'reinforce' or 'ppo' selects the softmax
         rule of agent/agent.py:77-97 instead of argmax / epsilon-greedy (:68-75)."""
         import ctypes as C
 
@@ -137,7 +137,7 @@ class FusedAgents:
         self.net = (net or AgentRNN(rnn_input_shape(args), args)).to(self.device)
         self.seed, self.calls = int(seed), 0
         self.row0 = int(env_offset) * self.n_agents
-        self.softmax = getattr(args, "alg", None) == "reinforce"
+        self.softmax = getattr(args, "alg", None) in ("reinforce", "ppo")
         self.hidden = torch.zeros(self.rows, 64, device=self.device)
         # previous action on entry (-1 = none), chosen action on return: the kernel updates it in place
         self.actions = torch.full((self.batch, self.n_agents), -1, dtype=torch.int64, device=self.device)

@@ -32,6 +32,7 @@ namespace {
 #include "policy_dev.h"
 #include "gru_seq.h"
 #include "returns.h"
+#include "ppo.h"
 
 struct PolicyParams {
     int rows, n_agents, n_actions, obs_stride, obs_offset;  // obs row r starts at obs + r*obs_stride + obs_offset (4 floats)
@@ -502,7 +503,7 @@ __global__ __launch_bounds__(KBLOCK) void k_policy_pack(PackParams p) {
 }
 
 thread_local char g_perr[200] = "";
-thread_local char g_lerr[200] = "";   // cs_gru_seq_*, cs_episode_returns
+thread_local char g_lerr[200] = "";   // cs_gru_seq_*, cs_episode_returns, cs_gae, cs_ppo_loss
 
 // persistent grid: as many blocks as the device holds at once (queried once)
 template <typename K>
@@ -512,6 +513,20 @@ int resident_blocks(K kernel) {
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, PBLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 2;
     return cus * per_cu;
+}
+
+// k_ppo_loss for the row width at hand (cs_ppo_loss has checked 2 <= n_actions <= 8)
+template <bool FULL>
+void ppo_launch(int n_actions, dim3 grid, hipStream_t stream, const PpoParams &p) {
+    switch (n_actions) {
+        case 2: hipLaunchKernelGGL((k_ppo_loss<2, FULL>), grid, dim3(PPO_BLOCK), 0, stream, p); break;
+        case 3: hipLaunchKernelGGL((k_ppo_loss<3, FULL>), grid, dim3(PPO_BLOCK), 0, stream, p); break;
+        case 4: hipLaunchKernelGGL((k_ppo_loss<4, FULL>), grid, dim3(PPO_BLOCK), 0, stream, p); break;
+        case 5: hipLaunchKernelGGL((k_ppo_loss<5, FULL>), grid, dim3(PPO_BLOCK), 0, stream, p); break;
+        case 6: hipLaunchKernelGGL((k_ppo_loss<6, FULL>), grid, dim3(PPO_BLOCK), 0, stream, p); break;
+        case 7: hipLaunchKernelGGL((k_ppo_loss<7, FULL>), grid, dim3(PPO_BLOCK), 0, stream, p); break;
+        default: hipLaunchKernelGGL((k_ppo_loss<8, FULL>), grid, dim3(PPO_BLOCK), 0, stream, p); break;
+    }
 }
 
 }  // namespace
@@ -746,6 +761,70 @@ int cs_episode_returns(const float *r, const float *terminated, const float *pad
     if (hipGetLastError() != hipSuccess) {
         snprintf(g_lerr, sizeof(g_lerr), "cs_episode_returns: kernel launch failed");
         return CS_E_LAUNCH;
+    }
+    return CS_OK;
+}
+
+// ---- PPO learner: advantages / value targets over t, and the clipped surrogate with its gradient (ppo.h) --------------------
+int cs_gae(const float *r, const float *terminated, const float *padded, const float *v, const float *v_next, int E, int T,
+           float gamma, float lambda, float *adv_out, float *ret_out, void *stream) {
+    if (!r || !terminated || !padded || !v || !v_next || !adv_out || !ret_out || E < 1 || T < 1) {
+        snprintf(g_lerr, sizeof(g_lerr), "cs_gae: bad argument (E = %d, T = %d; no pointer may be null)", E, T);
+        return CS_E_ARG;
+    }
+    const GaeParams p{r, terminated, padded, v, v_next, adv_out, ret_out, E, T, gamma, lambda};
+    hipLaunchKernelGGL(k_gae, dim3((E + RBLOCK - 1) / RBLOCK), dim3(RBLOCK), 0, (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_lerr, sizeof(g_lerr), "cs_gae: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    return CS_OK;
+}
+
+int cs_ppo_loss(const float *logits, const float *avail, const int64_t *u, const float *old_logp, const float *adv,
+                const float *mask, int64_t rows, int n_agents, int n_actions, float clip, float ent_coef, float epsilon,
+                const float *epsilon_dev, const float *inv_count_dev, float *dlogits_out, float *logp_out, float *stats_out,
+                float *scratch_dev, int64_t scratch_floats, void *stream) {
+    const int64_t max_rows = (int64_t)0x7fffffff / CS_PPO_BLOCK * CS_PPO_BLOCK;   // the grid's x extent is an int
+    if (!logits || !avail || !u || !mask || rows < 1 || rows > max_rows || n_agents < 1 || rows % n_agents != 0 || n_actions < 2 ||
+        n_actions > 8) {
+        snprintf(g_lerr, sizeof(g_lerr), "cs_ppo_loss: bad argument (rows = %lld, n_agents = %d, n_actions = %d: rows a multiple of "
+                 "n_agents, 2 to 8 actions; logits, avail, u, mask must be set)", (long long)rows, n_agents, n_actions);
+        return CS_E_ARG;
+    }
+    const int blocks = (int)((rows + CS_PPO_BLOCK - 1) / CS_PPO_BLOCK);
+    PpoParams p{logits, avail, u, old_logp, adv, mask, epsilon_dev, inv_count_dev, dlogits_out, logp_out, scratch_dev,
+                (long long)rows, n_agents, clip, ent_coef, epsilon};
+    if (!old_logp) {   // the no-grad pass: log pi(u) only
+        if (!logp_out) {
+            snprintf(g_lerr, sizeof(g_lerr), "cs_ppo_loss: bad argument (old_logp null: logp_out must be set)");
+            return CS_E_ARG;
+        }
+        ppo_launch<false>(n_actions, dim3(blocks), (hipStream_t)stream, p);
+    } else {
+        if (!adv || !inv_count_dev || !dlogits_out || !stats_out || !scratch_dev) {
+            snprintf(g_lerr, sizeof(g_lerr), "cs_ppo_loss: bad argument (with old_logp: adv, inv_count_dev, dlogits_out, stats_out, "
+                     "scratch_dev must be set)");
+            return CS_E_ARG;
+        }
+        if (scratch_floats < (int64_t)blocks * 4) {
+            snprintf(g_lerr, sizeof(g_lerr), "cs_ppo_loss: scratch holds %lld floats, %lld needed (4 per CS_PPO_BLOCK rows)",
+                     (long long)scratch_floats, (long long)blocks * 4);
+            return CS_E_ARG;
+        }
+        ppo_launch<true>(n_actions, dim3(blocks), (hipStream_t)stream, p);
+    }
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_lerr, sizeof(g_lerr), "cs_ppo_loss: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    if (old_logp) {
+        const PpoFinishParams f{scratch_dev, inv_count_dev, stats_out, blocks};
+        hipLaunchKernelGGL(k_ppo_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, f);
+        if (hipGetLastError() != hipSuccess) {
+            snprintf(g_lerr, sizeof(g_lerr), "cs_ppo_loss: reduction launch failed");
+            return CS_E_LAUNCH;
+        }
     }
     return CS_OK;
 }

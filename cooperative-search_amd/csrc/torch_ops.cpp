@@ -660,6 +660,61 @@ void episode_returns(const Tensor &r, const Tensor &terminated, const Tensor &pa
     TORCH_CHECK(rc == CS_OK, cs_learn_last_error());
 }
 
+// ---- PPO learner: advantages / value targets (cs_gae) and the clipped surrogate with its gradient (cs_ppo_loss) -------------
+void gae(const Tensor &r, const Tensor &terminated, const Tensor &padded, const Tensor &v, const Tensor &v_next, int64_t E, int64_t T,
+         double gamma, double gae_lambda, Tensor adv, Tensor ret) {
+    TORCH_CHECK(r.is_cuda(), "coopsearch: r must be a GPU tensor");
+    TORCH_CHECK(E >= 1 && T >= 1, "coopsearch: E and T must be >= 1");
+    check_f32(r, "r", E * T, r);
+    check_f32(terminated, "terminated", E * T, r);
+    check_f32(padded, "padded", E * T, r);
+    check_f32(v, "v", E * T, r);
+    check_f32(v_next, "v_next", E * T, r);
+    check_f32(adv, "adv", E * T, r);
+    check_f32(ret, "ret", E * T, r);
+    const int rc = cs_gae(r.data_ptr<float>(), terminated.data_ptr<float>(), padded.data_ptr<float>(), v.data_ptr<float>(),
+                          v_next.data_ptr<float>(), (int)E, (int)T, (float)gamma, (float)gae_lambda, adv.data_ptr<float>(),
+                          ret.data_ptr<float>(), stream_of(r));
+    TORCH_CHECK(rc == CS_OK, cs_learn_last_error());
+}
+
+void ppo_loss(const Tensor &logits, const Tensor &avail, const Tensor &u, const c10::optional<Tensor> &old_logp,
+              const c10::optional<Tensor> &adv, const Tensor &mask, int64_t rows, int64_t n_agents, int64_t n_actions, double clip,
+              double ent_coef, double epsilon, const c10::optional<Tensor> &epsilon_t, const c10::optional<Tensor> &inv_count,
+              c10::optional<Tensor> dlogits, c10::optional<Tensor> logp_out, c10::optional<Tensor> stats,
+              c10::optional<Tensor> scratch) {
+    auto has = [](const c10::optional<Tensor> &t) { return t.has_value() && t->defined(); };
+    TORCH_CHECK(logits.is_cuda(), "coopsearch: logits must be a GPU tensor");
+    TORCH_CHECK(rows >= 1 && n_agents >= 1 && rows % n_agents == 0, "coopsearch: rows must be a positive multiple of n_agents");
+    TORCH_CHECK(n_actions >= 2 && n_actions <= 8, "coopsearch: n_actions must be 2 to 8");
+    check_f32(logits, "logits", rows * n_actions, logits);
+    check_f32(avail, "avail", rows * n_actions, logits);
+    check_dev(u, "u", at::kLong, rows, logits);
+    check_f32(mask, "mask", rows / n_agents, logits);
+    if (has(epsilon_t)) check_f32(*epsilon_t, "epsilon_t", 1, logits);
+    if (has(logp_out)) check_f32(*logp_out, "logp_out", rows, logits);
+    int64_t scratch_floats = 0;
+    if (has(old_logp)) {
+        TORCH_CHECK(has(adv) && has(inv_count) && has(dlogits) && has(stats) && has(scratch),
+                    "coopsearch: with old_logp, adv, inv_count, dlogits, stats and scratch must be given");
+        check_f32(*old_logp, "old_logp", rows, logits);
+        check_f32(*adv, "adv", rows / n_agents, logits);
+        check_f32(*inv_count, "inv_count", 1, logits);
+        check_f32(*dlogits, "dlogits", rows * n_actions, logits);
+        check_f32(*stats, "stats", 4, logits);
+        check_f32(*scratch, "scratch", -1, logits);
+        scratch_floats = scratch->numel();
+    } else {
+        TORCH_CHECK(has(logp_out), "coopsearch: without old_logp, logp_out must be given");
+    }
+    const int rc = cs_ppo_loss(logits.data_ptr<float>(), avail.data_ptr<float>(), u.data_ptr<int64_t>(), opt_ptr<const float>(old_logp),
+                               opt_ptr<const float>(adv), mask.data_ptr<float>(), rows, (int)n_agents, (int)n_actions, (float)clip,
+                               (float)ent_coef, (float)epsilon, opt_ptr<const float>(epsilon_t), opt_ptr<const float>(inv_count),
+                               opt_ptr<float>(dlogits), opt_ptr<float>(logp_out), opt_ptr<float>(stats), opt_ptr<float>(scratch),
+                               scratch_floats, stream_of(logits));
+    TORCH_CHECK(rc == CS_OK, cs_learn_last_error());
+}
+
 }  // namespace
 
 TORCH_LIBRARY(coopsearch, m) {
@@ -720,4 +775,9 @@ TORCH_LIBRARY(coopsearch, m) {
           "Tensor(a!) dgi_out, Tensor(b!) dgh_out, Tensor(c!)? dh0_out) -> ()", &gru_seq_backward);
     m.def("episode_returns(Tensor r, Tensor terminated, Tensor padded, Tensor? q, int E, int T, float gamma, float td_lambda, "
           "Tensor(a!) out) -> ()", &episode_returns);
+    m.def("gae(Tensor r, Tensor terminated, Tensor padded, Tensor v, Tensor v_next, int E, int T, float gamma, float gae_lambda, "
+          "Tensor(a!) adv, Tensor(b!) ret) -> ()", &gae);
+    m.def("ppo_loss(Tensor logits, Tensor avail, Tensor u, Tensor? old_logp, Tensor? adv, Tensor mask, int rows, int n_agents, "
+          "int n_actions, float clip, float ent_coef, float epsilon, Tensor? epsilon_t, Tensor? inv_count, Tensor(a!)? dlogits, "
+          "Tensor(b!)? logp_out, Tensor(c!)? stats, Tensor(d!)? scratch) -> ()", &ppo_loss);
 }

@@ -1,5 +1,5 @@
-"""QMIX, DOP and REINFORCE learners on the device: the consumers of DeviceReplayBuffer.sample() (policy/qmix.py, policy/dop.py,
-policy/reinforce.py of the reference).
+"""QMIX, DOP, REINFORCE and PPO learners on the device: the consumers of DeviceReplayBuffer.sample() (policy/qmix.py,
+policy/dop.py, policy/reinforce.py of the reference; PPO has no counterpart there).
 
 The reference's `learn` (policy/qmix.py:85-130) unrolls the agent network one transition at a time (`get_q_values`,
 :160-182): fc1 -> ReLU -> GRUCell -> fc2 for the eval and the target network on E*n rows per step, T = 200 steps, and autograd
@@ -21,6 +21,12 @@ over all rows in torch.
 Every `learn` also takes a batch in the map-once format of the flight variant (replay.COMPACT_KEYS) as
 it is.  QMIX and REINFORCE never build `o` / `o_next` from it: the conv front end runs once per (episode, step) on the map
 (`map_features`), its 16 features are broadcast over the agents, and the rest of the unroll is the one above.
+
+`PPOLearner` is the on-policy learner shaped like the batched env: a clipped-surrogate actor-critic
+with a central value function that reuses every collected episode for several epochs.  Its actor goes through the same
+unroll; its two other loops are HIP kernels of the returns' family (csrc/ppo.h): `gae` (cs_gae: advantages and value targets,
+one launch) and `PPOPolicyLoss` (cs_ppo_loss: the clipped surrogate, its entropy bonus, their statistics and the gradient
+with respect to the logits in one pass over the rows).
 
 `conv_impl="hip"` (opt-in on every learner) takes that conv front end from `ConvFeatures` instead of the
 torch modules: the acting kernel (k_conv_features) forward, k_conv_features_bwd (csrc/conv_bwd.h) backward, so that a flight
@@ -797,3 +803,230 @@ class ReinforceLearner:
 
     def load_model(self, rnn_root):
         self.eval_rnn.load_state_dict(torch.load(rnn_root, map_location=self.device))
+
+
+# ---- PPO with a central value function (MAPPO): no counterpart in the reference ----------------------------------------------
+
+def get_ppo_args(args, seed=None):
+    """The learner fields of PPOLearner on an argparse-style namespace, shaped like get_reinforce_args (on-policy, the same
+    actor); seed as get_dop_args.  Exploration comes from the sampled softmax policy itself: epsilon stays 0."""
+    args.off_policy = False
+    args.rnn_hidden_dim, args.critic_dim = 64, 128
+    args.lr_actor, args.lr_critic, args.gae_lambda = 5e-4, 1e-3, 0.95
+    args.ppo_clip, args.ppo_epochs, args.ppo_minibatches, args.ppo_entropy, args.ppo_norm_adv = 0.2, 4, 1, 0.01, True
+    args.gamma, args.optimizer = getattr(args, "gamma", 0.99), getattr(args, "optimizer", "Adam")
+    args.epsilon, args.anneal_epsilon, args.min_epsilon, args.epsilon_anneal_scale = 0, 0, 0, "epoch"
+    args.grad_norm_clip, args.n_episodes, args.evaluate_cycle, args.save_cycle = 10, 1, 200, 500
+    if seed is not None:
+        args.seed = seed
+    return args
+
+
+class ValueCritic(nn.Module):
+    """The central value function: state -> relu(fc1) -> relu(fc2) -> fc3 = V(s), one value per (episode, step)."""
+
+    def __init__(self, input_shape, args):
+        super().__init__()
+        self.args = args
+        self.fc1 = nn.Linear(input_shape, args.critic_dim)
+        self.fc2 = nn.Linear(args.critic_dim, args.critic_dim)
+        self.fc3 = nn.Linear(args.critic_dim, 1)
+
+    def forward(self, state):
+        return self.fc3(F.relu(self.fc2(F.relu(self.fc1(state)))))
+
+
+def gae(r, terminated, padded, v, v_next, gamma=0.99, gae_lambda=0.95):
+    """cs_gae (csrc/ppo.h) on device tensors: r, terminated, padded, v = V(s), v_next = V(s_next) [E, T] or [E, T, 1] float32
+    -> (adv, ret) [E, T]: generalised advantage estimates and the value targets adv + v, zero on padded steps.  One launch."""
+    E, T = int(r.shape[0]), int(r.shape[1])
+    flat = lambda x: x.detach().float().reshape(E, T).contiguous()
+    adv = torch.empty(E, T, dtype=torch.float32, device=r.device)
+    ret = torch.empty_like(adv)
+    _ops().gae(flat(r), flat(terminated), flat(padded), flat(v), flat(v_next), E, T, float(gamma), float(gae_lambda), adv, ret)
+    return adv, ret
+
+
+def gae_torch(r, terminated, padded, v, v_next, gamma, gae_lambda):
+    """cs_gae's recursion one step at a time, t = T-1 .. 0, in its evaluation order (csrc/ppo.h) -> (adv, ret) [E, T]."""
+    E = r.shape[0]
+    r, v, v_next = r.reshape(E, -1), v.reshape(E, -1), v_next.reshape(E, -1)
+    m, c = (1 - padded).reshape(E, -1), (1 - terminated).reshape(E, -1)
+    gl = torch.tensor(gamma, dtype=r.dtype) * torch.tensor(gae_lambda, dtype=r.dtype)   # rounded once, in r's precision
+    gl = gl.to(r.device)
+    delta = (r + (gamma * v_next) * c) - v
+    adv = torch.zeros_like(r)
+    adv[:, -1] = delta[:, -1] * m[:, -1]
+    for t in range(r.shape[1] - 2, -1, -1):
+        adv[:, t] = (delta[:, t] + (gl * adv[:, t + 1]) * c[:, t]) * m[:, t]
+    return adv, (adv + v) * m
+
+
+def ppo_policy_loss_torch(logits, avail_u, u, old_logp, adv, mask, clip, ent_coef, epsilon):
+    """PPO's actor loss in plain autograd, over action_prob / log_pi_taken: logits, avail_u [E, T, n, A], u [E, T, n, 1]
+    long, old_logp [E, T, n], adv, mask [E, T] (or [E, T, 1]) -> (loss, stats [4]).  loss = policy loss - ent_coef * mean
+    entropy; stats = (policy loss = -mean min(ratio adv, clamp(ratio, 1 - clip, 1 + clip) adv), mean entropy, fraction of
+    rows whose ratio lies outside the clip range, mean(old_logp - logp)), means over the n * sum(mask) live rows; detached."""
+    E, T, n = logits.shape[:3]
+    m = mask.reshape(E, T, 1).expand(E, T, n)
+    a = adv.reshape(E, T, 1)
+    prob = action_prob(logits, avail_u, epsilon)
+    logp = log_pi_taken(prob, u, m)
+    ratio = torch.exp(logp - old_logp)
+    surr = torch.minimum(ratio * a, torch.clamp(ratio, 1 - clip, 1 + clip) * a)
+    entropy = -(prob * torch.log(prob.masked_fill(prob <= 0, 1.0))).sum(dim=-1)   # 0 log 0 = 0
+    inv_count = 1 / (n * mask.sum())
+    policy_loss = -(surr * m).sum() * inv_count
+    mean_entropy = (entropy * m).sum() * inv_count
+    outside = ((ratio < 1 - clip) | (ratio > 1 + clip)).to(logits.dtype)
+    stats = torch.stack([policy_loss, mean_entropy, (outside * m).sum() * inv_count, ((old_logp - logp) * m).sum() * inv_count])
+    return policy_loss - ent_coef * mean_entropy, stats.detach()
+
+
+def _ppo_rows(logits, avail_u, u, mask, epsilon):
+    """cs_ppo_loss's view of the tensors above: (logits, avail [R, A], u [R], mask [E*T], rows, n, A, epsilon, epsilon_t)."""
+    E, T, n, A = (int(x) for x in logits.shape)
+    f32 = lambda x, *shape: x.detach().float().reshape(*shape).contiguous()
+    eps_t = f32(epsilon, -1)[:1] if torch.is_tensor(epsilon) else None   # a device scalar stays on the device
+    return (f32(logits, E * T * n, A), f32(avail_u, E * T * n, A), u.detach().reshape(E * T * n).contiguous(), f32(mask, E * T),
+            E * T * n, n, A, 0.0 if eps_t is not None else float(epsilon), eps_t)
+
+
+def ppo_logp(logits, avail_u, u, mask, epsilon):
+    """log pi(u) [E, T, n] of the action probabilities (action_prob / log_pi_taken; 0 on padded steps) from cs_ppo_loss's
+    no-grad mode: the instructions that compute logp inside PPOPolicyLoss, so an unchanged policy has ratio exactly 1."""
+    z, av, uu, m, rows, n, A, eps, eps_t = _ppo_rows(logits, avail_u, u, mask, epsilon)
+    out = z.new_empty(rows)
+    _ops().ppo_loss(z, av, uu, None, None, m, rows, n, A, 0.0, 0.0, eps, eps_t, None, None, out, None, None)
+    return out.view(logits.shape[:3])
+
+
+PPO_BLOCK = 256   # CS_PPO_BLOCK of include/coopsearch.h: rows per partial of cs_ppo_loss's scratch buffer
+
+
+class PPOPolicyLoss(torch.autograd.Function):
+    """ppo_policy_loss_torch on cs_ppo_loss (csrc/ppo.h): (logits, avail_u, u, old_logp, adv, mask, clip, ent_coef, epsilon,
+    inv_count) -> (loss, stats [4]); inv_count: the device scalar 1 / (n * sum(mask)).  One pass over the rows computes the
+    loss's sums and dloss/dlogits; backward is grad_out * dlogits.  stats carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, avail_u, u, old_logp, adv, mask, clip, ent_coef, epsilon, inv_count):
+        z, av, uu, m, rows, n, A, eps, eps_t = _ppo_rows(logits, avail_u, u, mask, epsilon)
+        f32 = lambda x, k: x.detach().float().reshape(k).contiguous()
+        dlogits, stats = torch.empty_like(z), z.new_empty(4)
+        scratch = z.new_empty(4 * ((rows + PPO_BLOCK - 1) // PPO_BLOCK))
+        _ops().ppo_loss(z, av, uu, f32(old_logp, rows), f32(adv, rows // n), m, rows, n, A, float(clip), float(ent_coef), eps, eps_t,
+                        f32(inv_count, 1), dlogits, None, stats, scratch)
+        ctx.save_for_backward(dlogits.view(logits.shape))
+        ctx.mark_non_differentiable(stats)
+        return stats[0] - float(ent_coef) * stats[1], stats
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_stats):
+        (dlogits,) = ctx.saved_tensors
+        return (grad_loss * dlogits,) + (None,) * 9
+
+
+class PPOLearner:
+    """A clipped-surrogate actor-critic with a central value function (PPO; MAPPO for the team) on the device.  args: the
+    namespace after get_ppo_args (seed, lr_actor, lr_critic, gamma, gae_lambda, ppo_clip, ppo_epochs, ppo_minibatches,
+    ppo_entropy, ppo_norm_adv, grad_norm_clip, critic_dim, rnn_hidden_dim, optimizer) and the env fields.  On-policy: `learn`
+    takes the episode dict that EpisodeCollector.generate_episodes returns and reuses it for ppo_epochs epochs.  The actor is
+    REINFORCE's (the same initial parameters for the same seed, the same checkpoint file).  unroll: "fused" (GRUSequence,
+    cs_gae, cs_ppo_loss; needs the HIP library and a GPU) or "torch" (the reference-style step loops and plain autograd over
+    the same modules; also runs on the CPU).  conv_impl: as QMixLearner's."""
+
+    def __init__(self, args, device="cuda", unroll="fused", conv_impl="torch"):
+        if unroll not in ("fused", "torch"):
+            raise ValueError("unroll must be 'fused' or 'torch'")
+        self.conv_impl = check_conv_impl(args, device, unroll, conv_impl)
+        self.args, self.device, self.unroll = args, torch.device(device), unroll
+        self.n_actions, self.n_agents = args.n_actions, args.n_agents
+        self.state_shape, self.obs_shape = args.state_shape, args.obs_shape
+        torch.manual_seed(args.seed)   # the actor first: ReinforceLearner's initial parameters
+        self.eval_rnn = AgentRNN(rnn_input_shape(args), args).to(self.device)
+        self.critic = ValueCritic(self.state_shape, args).to(self.device)
+        self.eval_rnn.conv_impl = self.conv_impl   # read by map_features / unroll_q
+        self.model_dir = model_dir(args, "ppo")
+        self.rnn_parameters = list(self.eval_rnn.parameters())
+        self.critic_parameters = list(self.critic.parameters())
+        self.rnn_optimizer = _make_optimizer(args, self.rnn_parameters, args.lr_actor)
+        self.critic_optimizer = _make_optimizer(args, self.critic_parameters, args.lr_critic)
+        self.last_actor_grad_norm = self.last_critic_grad_norm = None
+
+    def advantages(self, batch, v, v_next):
+        """(adv, ret) [E, T] from the batch's rewards and the critic's values (no graph)."""
+        a = self.args
+        fn = gae if self.unroll == "fused" else gae_torch
+        return fn(batch["r"], batch["terminated"], batch["padded"], v, v_next, a.gamma, a.gae_lambda)
+
+    def policy_loss(self, logits, avail_u, u, old_logp, adv, mask, epsilon):
+        """(loss, stats [4]) of one group of episodes: PPOPolicyLoss, or its plain-autograd twin."""
+        a = self.args
+        if self.unroll == "fused":
+            inv_count = 1 / (self.n_agents * mask.sum())
+            return PPOPolicyLoss.apply(logits, avail_u, u, old_logp, adv, mask, a.ppo_clip, a.ppo_entropy, epsilon, inv_count)
+        return ppo_policy_loss_torch(logits, avail_u, u, old_logp, adv, mask, a.ppo_clip, a.ppo_entropy, epsilon)
+
+    def learn(self, batch, max_episode_len=None, train_step=0, epsilon=0.0):
+        """ppo_epochs x ppo_minibatches updates of the actor and the critic on a dense or a map-once episode dict.  Once, without
+        a graph: V(s), V(s_next), log pi_old(u), the advantages and value targets (GAE), the advantages standardised over the
+        live steps when args.ppo_norm_adv.  Then every epoch splits the episodes into ppo_minibatches groups of whole episodes
+        (torch.randperm on the device's global generator; no draw for one group) and steps both networks on each: the actor
+        on the clipped surrogate minus ppo_entropy * entropy, the critic on 0.5 sum((V(s) - ret)^2 m) / sum(m), each clipped
+        to grad_norm_clip.  epsilon: a float or a device scalar (action_prob's mix).  Returns a device tensor [ppo_epochs, 5]:
+        policy loss, mean entropy, clip fraction, mean(log pi_old - log pi), value loss, averaged over the epoch's groups (no
+        host synchronisation)."""
+        a, n = self.args, self.n_agents
+        batch, T, u, mask1 = _prepare(batch, self.device, max_episode_len, n, self.n_actions, self.eval_rnn.fc1.weight.dtype)
+        E = int(u.shape[0])
+        mask = mask1.reshape(E, T)
+        fused = self.unroll == "fused"
+        with torch.no_grad():
+            v, v_next = self.critic(batch["s"]).reshape(E, T), self.critic(batch["s_next"]).reshape(E, T)
+            logits = _policy_logits(self.eval_rnn, a, n, batch, T, self.unroll)
+            if fused:
+                old_logp = ppo_logp(logits, batch["avail_u"], u, mask, epsilon)
+            else:
+                old_logp = log_pi_taken(action_prob(logits, batch["avail_u"], epsilon), u, mask1.expand(E, T, n))
+            adv, ret = self.advantages(batch, v, v_next)
+            if a.ppo_norm_adv:
+                count = mask.sum()
+                mean = (adv * mask).sum() / count
+                std = ((((adv - mean) * mask) ** 2).sum() / count).sqrt()
+                adv = (adv - mean) / (std + 1e-8) * mask
+        groups = int(a.ppo_minibatches)
+        out = []
+        for _ in range(int(a.ppo_epochs)):
+            parts = [None] if groups == 1 else torch.randperm(E, device=self.device).chunk(groups)
+            rows = []
+            for idx in parts:
+                take = (lambda x: x) if idx is None else (lambda x: x.index_select(0, idx))
+                b = batch if idx is None else {k: take(x) for k, x in batch.items()}
+                m = take(mask)
+                logits = _policy_logits(self.eval_rnn, a, n, b, T, self.unroll)
+                loss, stats = self.policy_loss(logits, b["avail_u"], b["u"], take(old_logp), take(adv), m, epsilon)
+                self.rnn_optimizer.zero_grad()
+                loss.backward()
+                self.last_actor_grad_norm = torch.nn.utils.clip_grad_norm_(self.rnn_parameters, a.grad_norm_clip)
+                self.rnn_optimizer.step()
+                value = self.critic(b["s"]).reshape(m.shape)
+                value_loss = 0.5 * (((value - take(ret)) * m) ** 2).sum() / m.sum()
+                self.critic_optimizer.zero_grad()
+                value_loss.backward()
+                self.last_critic_grad_norm = torch.nn.utils.clip_grad_norm_(self.critic_parameters, a.grad_norm_clip)
+                self.critic_optimizer.step()
+                rows.append(torch.cat([stats, value_loss.detach().reshape(1)]))
+            out.append(rows[0] if len(rows) == 1 else torch.stack(rows).mean(0))
+        return torch.stack(out)
+
+    def save_model(self, num):
+        """<model_dir>/<num>_rnn_net_params.pkl (the reference's actor file: its loader and Runner.replay read it) and
+        <num>_critic_net_params.pkl."""
+        os.makedirs(self.model_dir, exist_ok=True)
+        torch.save(self.eval_rnn.state_dict(), os.path.join(self.model_dir, str(num) + "_rnn_net_params.pkl"))
+        torch.save(self.critic.state_dict(), os.path.join(self.model_dir, str(num) + "_critic_net_params.pkl"))
+
+    def load_model(self, rnn_root, critic_root):
+        self.eval_rnn.load_state_dict(torch.load(rnn_root, map_location=self.device))
+        self.critic.load_state_dict(torch.load(critic_root, map_location=self.device))

@@ -23,16 +23,16 @@ import torch
 
 from .agents import FusedAgents
 from .collector import EpisodeCollector, EpsilonSchedule
-from .learner import DOPLearner, QMixLearner, ReinforceLearner
+from .learner import DOPLearner, PPOLearner, QMixLearner, ReinforceLearner
 from .replay import CompactReplayBuffer, DeviceReplayBuffer
 
 # fields the reference's get_mixer_args / get_common_args set and this package's get_*_args leave to the caller
 # (common/arguments.py:43-46, :84-104)
 RUN_DEFAULTS = dict(n_epoch=500000, n_episodes=1, train_steps=1, evaluate_cycle=200, save_cycle=500, evaluate_epoch=20,
                     model_dir="./model/", result_dir="./result/", load_model=False, compact_episodes=False)
-LEARNERS = {"qmix": QMixLearner, "dop": DOPLearner, "reinforce": ReinforceLearner}
+LEARNERS = {"qmix": QMixLearner, "dop": DOPLearner, "reinforce": ReinforceLearner, "ppo": PPOLearner}
 # the checkpoint file whose presence get_model_idx() - 1 must show when resuming (the reference learners' __init__)
-_RESUME = {"qmix": ("rnn", "qmix"), "dop": ("actor", "critic", "mixer"), "reinforce": ("rnn",)}
+_RESUME = {"qmix": ("rnn", "qmix"), "dop": ("actor", "critic", "mixer"), "reinforce": ("rnn",), "ppo": ("rnn", "critic")}
 
 
 def run_name(args):
@@ -97,7 +97,7 @@ def apply_run_defaults(args):
 
 class Runner:
     """Runner(env, args): `env` a BatchedFlightEnv; `args` the reference's namespace after get_mixer_args / get_dop_args /
-    get_reinforce_args and apply_env_info; args.alg selects the learner.  The parts (learner, agents, schedule, collector,
+    get_reinforce_args / get_ppo_args and apply_env_info; args.alg selects the learner.  The parts (learner, agents, schedule, collector,
     buffer) are built here unless passed in.  args.compact_episodes (flight only; default False): episodes are collected,
     stored and learnt from in the map-once format (replay.COMPACT_KEYS) -- a CompactReplayBuffer and
     generate_episodes(compact=True); the schedule of calls is the same.  args.conv_impl (absent: "torch") goes to the learner.
@@ -110,7 +110,7 @@ class Runner:
         if alg in ("vdn", "random"):
             raise ValueError(f"Runner: alg {alg!r} is not trained here (VDN and random have no device learner)")
         if alg not in LEARNERS:
-            raise ValueError(f"Runner: no such algorithm {alg!r} (qmix, dop or reinforce)")
+            raise ValueError(f"Runner: no such algorithm {alg!r} (qmix, dop, reinforce or ppo)")
         self.env, self.args = env, apply_run_defaults(args)
         device = getattr(env, "device", "cuda")
         if learner is None:   # args.conv_impl (absent: "torch"): the learners' conv front end, learner.check_conv_impl
@@ -243,7 +243,7 @@ class Runner:
         return train_steps
 
     def train(self, batch, train_step):
-        """agent.py:112-136: one learn call (QMIX without epsilon, DOP and REINFORCE with env 0's), the acting network repacked,
+        """agent.py:112-136: one learn call (QMIX without epsilon, DOP, REINFORCE and PPO with env 0's), the acting network repacked,
         a checkpoint when train_step > 0 and train_step % save_cycle == 0."""
         if self.args.alg == "qmix":
             self.learner.learn(batch, None, train_step)

@@ -39,7 +39,7 @@ extern "C" {
                               still 7: cs_gru_seq_forward, cs_gru_seq_backward, cs_learn_last_error were ADDED, then
                               cs_episode_returns, then cs_policy_pack_device, then cs_collect_flight, cs_compact_out and
                               cs_store_episodes_compact, then cs_snapshot_bytes, cs_snapshot and cs_restore, then cs_render_params and
-                              cs_render_episodes (no existing export or struct changed: a version-7 caller works unchanged) */
+                              cs_render_episodes, then cs_gae and cs_ppo_loss (no existing export or struct changed: a version-7 caller works unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
 #define CS_MAX_MAP 64
@@ -523,6 +523,36 @@ int cs_gru_seq_backward(const float *w_hh, const float *dh_seq, const float *h_s
  * bit-identical); no atomics, so reruns are bit-identical.  lambda is ignored when q is NULL. */
 int cs_episode_returns(const float *r, const float *terminated, const float *padded, const float *q, int E, int T,
                        float gamma, float lambda, float *out, void *stream);
+/* PPO learner (learner.PPOLearner): generalised advantage estimation, ONE launch for all E episodes and T steps.
+ * r, terminated, padded, v = V(s), v_next = V(s_next) [E][T] float32 -> adv_out, ret_out [E][T].  With m = 1 - padded,
+ * c = 1 - terminated, gl = gamma * lambda, in fp32 in this order (no fused multiply-adds: a float32 restatement is
+ * bit-identical; csrc/ppo.h):
+ *   delta = (r + (gamma * v_next) * c) - v
+ *   A[T-1] = delta * m,  A[t] = (delta + (gl * A[t+1]) * c) * m,  ret = (A + v) * m
+ * With v = v_next = 0 and lambda = 1, adv_out equals cs_episode_returns' REINFORCE return bit for bit.  Padded steps are
+ * exactly zero (finite inputs).  No atomics: reruns are bit-identical. */
+int cs_gae(const float *r, const float *terminated, const float *padded, const float *v, const float *v_next, int E, int T,
+           float gamma, float lambda, float *adv_out, float *ret_out, void *stream);
+/* PPO's clipped surrogate with an entropy bonus, its statistics and its gradient with respect to the logits, in one pass over
+ * the rows = E * T * n_agents rows (row rho belongs to step rho / n_agents).  logits, avail [rows][n_actions] float32 (2 to 8
+ * actions), u [rows] int64, old_logp [rows] or NULL, adv, mask [rows / n_agents].  epsilon (the exploration mix of the
+ * action probabilities) is read from epsilon_dev[0] when that is set, else from `epsilon`; inv_count_dev[0] =
+ * 1 / (n_agents * sum(mask)), a device scalar.  Per row with mask != 0: p = the reference actors' action probabilities
+ * (softmax, epsilon mix over the available actions, unavailable ones zeroed, renormalised), logp = log p[u],
+ * ratio = exp(logp - old_logp), surr = min(ratio adv, clamp(ratio, 1 - clip, 1 + clip) adv), H = -sum p log p.
+ *   old_logp == NULL: only logp_out [rows] is written (the no-grad pass; adv, inv_count_dev and the outputs below unused).
+ *   old_logp != NULL: dlogits_out [rows][n_actions] = d(inv_count * sum mask (-surr - ent_coef H)) / dlogits, the gradient
+ *     passing where the unclipped term is the active one (both clip boundaries included: torch.clamp / torch.minimum);
+ *     stats_out [4] = (policy loss = -mean surr, mean H, fraction of rows with ratio outside the clip range,
+ *     mean(old_logp - logp)), means over the live rows; logp_out [rows] or NULL.
+ * Rows with mask == 0 give zeros everywhere, whatever their other inputs hold.  scratch_dev: scratch_floats >=
+ * 4 * ceil(rows / CS_PPO_BLOCK) floats (one partial per block; a second one-block launch adds them in a fixed order).  No
+ * atomics: reruns are bit-identical. */
+#define CS_PPO_BLOCK 256
+int cs_ppo_loss(const float *logits, const float *avail, const int64_t *u, const float *old_logp, const float *adv,
+                const float *mask, int64_t rows, int n_agents, int n_actions, float clip, float ent_coef, float epsilon,
+                const float *epsilon_dev, const float *inv_count_dev, float *dlogits_out, float *logp_out, float *stats_out,
+                float *scratch_dev, int64_t scratch_floats, void *stream);
 const char *cs_learn_last_error(void);
 
 #ifdef __cplusplus

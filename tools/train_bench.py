@@ -7,11 +7,11 @@ defaults); the ring holds max(buffer_size, B) episodes.  Epochs are timed in win
 HIP events (what the host can enqueue ahead shows up there); ms/epoch = the median window / window.  Also times one repack
 either way: the pack kernel under HIP events, the host pack with a wall clock (it blocks the host).  Prints ONE JSON line.
 
---curve: instead, one QMIX learning curve (flight_easy, 3 agents, B = 256): targets_find of every evaluation of Runner.run,
+--curve: instead, one learning curve of --alg (flight_easy, 3 agents, B = 256): targets_find of every evaluation of Runner.run,
 next to the random policy under the same evaluation.
 
-    python tools/train_bench.py [--alg qmix|dop|reinforce] [--warmup 10] [--windows 5] [--window 5] [--batches 32,256,4096]
-    python tools/train_bench.py --curve [--epochs 3000] [--evaluate-cycle 100]
+    python tools/train_bench.py [--alg qmix|dop|reinforce|ppo] [--warmup 10] [--windows 5] [--window 5] [--batches 32,256,4096]
+    python tools/train_bench.py --curve [--alg qmix] [--epochs 3000] [--evaluate-cycle 100]
 """
 import argparse
 import json
@@ -24,7 +24,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-ARGS_FN = {"qmix": "get_mixer_args", "dop": "get_dop_args", "reinforce": "get_reinforce_args"}
+ARGS_FN = {"qmix": "get_mixer_args", "dop": "get_dop_args", "reinforce": "get_reinforce_args", "ppo": "get_ppo_args"}
 
 
 def make_runner(alg, B, root, seed=1, **over):
@@ -35,7 +35,8 @@ def make_runner(alg, B, root, seed=1, **over):
     cs.apply_env_info(args, env)
     args.alg = alg
     getattr(cs, ARGS_FN[alg])(args, seed=seed)
-    args.buffer_size = max(args.buffer_size, B)
+    if hasattr(args, "buffer_size"):   # (PPO keeps no ring)
+        args.buffer_size = max(args.buffer_size, B)
     args.model_dir, args.result_dir = os.path.join(root, "model") + "/", os.path.join(root, "result") + "/"
     args.save_cycle = 10 ** 9   # no checkpoints inside the timed epochs
     for k, v in over.items():
@@ -110,7 +111,7 @@ def curve(a):
     import torch
     import cooperative_search_amd as cs
     with tempfile.TemporaryDirectory() as root:
-        r, env = make_runner("qmix", a.curve_batch, root, seed=a.seed, evaluate_cycle=a.evaluate_cycle)
+        r, env = make_runner(a.alg, a.curve_batch, root, seed=a.seed, evaluate_cycle=a.evaluate_cycle)
         ev = r.evaluate
 
         def evaluate():   # progress on stderr, one line per evaluation
@@ -124,9 +125,9 @@ def curve(a):
         g = torch.Generator("cuda").manual_seed(5)
         batches = max(1, math.ceil(r.args.evaluate_epoch / env.batch))
         rand = [cs.evaluate(env, cs.random_policy(g), batches) for _ in range(5)]
-    return dict(tool="train_bench --curve", alg="qmix", env="flight_easy", n_agents=3, B=a.curve_batch, seed=a.seed,
+    return dict(tool="train_bench --curve", alg=a.alg, env="flight_easy", n_agents=3, B=a.curve_batch, seed=a.seed,
                 epochs=a.epochs, evaluate_cycle=a.evaluate_cycle, evaluate_episodes=batches * a.curve_batch,
-                train_steps_per_epoch=r.args.train_steps, batch_size=r.args.batch_size, wall_s=round(wall, 1),
+                train_steps_per_epoch=r.args.train_steps, batch_size=getattr(r.args, "batch_size", a.curve_batch), wall_s=round(wall, 1),
                 targets_find=[round(v, 4) for v in r.targets_find], episode_reward=[round(v, 3) for v in r.episode_rewards],
                 win_rate=[round(v, 4) for v in r.win_rates],
                 random_policy_targets_find=[round(x[2], 4) for x in rand],
