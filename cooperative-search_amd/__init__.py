@@ -18,6 +18,7 @@ from .learner import DOPLearner, OffPGCritic, ReinforceLearner, get_dop_args, ge
 from .learner import PPOLearner, PPOPolicyLoss, ValueCritic, gae, get_ppo_args  # noqa: F401
 from .runner import Runner, get_model_idx, run_name  # noqa: F401
 from .snapshot import EnvSnapshot  # noqa: F401
+from .baseline import CoverageAgents, coverage_actions_torch  # noqa: F401
 from .render import RenderSpec, episode_tables, render_episodes, render_episodes_torch, write_frames  # noqa: F401
 
 __all__ = ["BatchedFlightEnv", "FlightSearchEnvEasy", "FlightSearchEnv", "load_targets", "default_circle_dict",

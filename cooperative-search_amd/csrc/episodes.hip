@@ -152,6 +152,7 @@ __global__ __launch_bounds__(256) void k_compact_small(CompactParams p) {
 }
 
 #include "render.h"   // k_render_episodes: episode rows -> RGB frames (cs_render_episodes)
+#include "coverage.h" // k_coverage_actions: the greedy coverage baseline (cs_coverage_actions)
 
 thread_local char g_eerr[160] = "";
 
@@ -246,6 +247,36 @@ int cs_render_episodes(const cs_render_params *p, const float *states_dev, const
                        (hipStream_t)stream, a);
     if (hipGetLastError() != hipSuccess) {
         snprintf(g_eerr, sizeof(g_eerr), "cs_render_episodes: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    return CS_OK;
+}
+
+int cs_coverage_actions(const cs_coverage_params *p, const float *state_dev, int B, int32_t *grid_dev, int64_t *actions_dev,
+                        void *stream) {
+    const char *bad = nullptr;
+    if (!p || !state_dev || !grid_dev || !actions_dev) bad = "a NULL pointer";
+    else if (B < 1) bad = "B must be >= 1";
+    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
+    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
+    else if (p->view_range < 0 || p->view_range > CS_MAX_MAP) bad = "view_range must be 0..64";
+    else if (p->keep < 0 || p->keep > 65536) bad = "keep must be 0..65536";
+    else if (p->regrow < 1 || p->regrow > 16) bad = "regrow must be 1..16";
+    else if (p->lookahead < 0 || p->lookahead > p->side) bad = "lookahead must be 0..side";
+    else if (p->state_width < 4 * p->n_agents) bad = "state_width must be at least 4 n_agents";
+    else if (p->reserved != 0) bad = "reserved must be 0";
+    else if ((uintptr_t)grid_dev % 4 != 0 || (uintptr_t)state_dev % 4 != 0 || (uintptr_t)actions_dev % 8 != 0)
+        bad = "a pointer is not aligned to its element size";
+    if (bad) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_coverage_actions: %s", bad);
+        return CS_E_CONFIG;
+    }
+    const int cells = p->side * p->side;
+    const CoverageArgs a{state_dev, grid_dev, actions_dev, p->n_agents, p->side, p->state_width, 16 * p->view_range, p->keep, p->regrow,
+                         16 * p->lookahead, (cells % 4 == 0 && (uintptr_t)grid_dev % 16 == 0) ? 1 : 0};
+    hipLaunchKernelGGL(k_coverage_actions, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_coverage_actions: kernel launch failed");
         return CS_E_LAUNCH;
     }
     return CS_OK;

@@ -608,6 +608,36 @@ void render_episodes(const Tensor &states, const c10::optional<Tensor> &maps, co
     TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
 }
 
+// ---- greedy coverage baseline (cs_coverage_actions): state [B, S >= 4n] float32, grid [B, side * side] int32 (in / out),
+// actions [B, n] int64 (out).  What the shapes and integers say is checked first (nothing is dereferenced), then the tensors.
+void coverage_actions(const Tensor &state, Tensor grid, Tensor actions, int64_t n_agents, int64_t side, int64_t view_range, int64_t keep,
+                      int64_t regrow, int64_t lookahead) {
+    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: coverage_actions: n_agents must be 1..8, got ", n_agents);
+    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: coverage_actions: side must be 1..", CS_MAX_MAP, ", got ", side);
+    TORCH_CHECK(view_range >= 0 && view_range <= CS_MAX_MAP, "coopsearch: coverage_actions: view_range must be 0..", CS_MAX_MAP, ", got ",
+                view_range);
+    TORCH_CHECK(keep >= 0 && keep <= 65536, "coopsearch: coverage_actions: keep must be 0..65536, got ", keep);
+    TORCH_CHECK(regrow >= 1 && regrow <= 16, "coopsearch: coverage_actions: regrow must be 1..16, got ", regrow);
+    TORCH_CHECK(lookahead >= 0 && lookahead <= side, "coopsearch: coverage_actions: lookahead must be 0..side, got ", lookahead);
+    TORCH_CHECK(state.dim() == 2 && state.size(0) >= 1 && state.size(0) <= INT32_MAX && state.size(1) >= 4 * n_agents &&
+                    state.size(1) <= INT32_MAX,
+                "coopsearch: coverage_actions: state must be [B, S] with B >= 1 and S >= 4 n_agents = ", 4 * n_agents);
+    const int64_t B = state.size(0), S = state.size(1);
+    TORCH_CHECK(grid.dim() == 2 && grid.size(0) == B && grid.size(1) == side * side, "coopsearch: coverage_actions: grid must be [", B,
+                ", ", side * side, "]");
+    TORCH_CHECK(actions.dim() == 2 && actions.size(0) == B && actions.size(1) == n_agents, "coopsearch: coverage_actions: actions must be [",
+                B, ", ", n_agents, "]");
+    TORCH_CHECK(state.is_cuda(), "coopsearch: coverage_actions: state must be a GPU tensor");
+    check_f32(state, "state", B * S, state);
+    check_dev(grid, "grid", at::kInt, B * side * side, state);
+    check_dev(actions, "actions", at::kLong, B * n_agents, state);
+    const cs_coverage_params p{(int32_t)n_agents, (int32_t)side, (int32_t)view_range, (int32_t)keep, (int32_t)regrow, (int32_t)lookahead,
+                               (int32_t)S, 0};
+    const int rc = cs_coverage_actions(&p, state.data_ptr<float>(), (int)B, grid.data_ptr<int32_t>(), actions.data_ptr<int64_t>(),
+                                       stream_of(state));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
 int64_t abi_version() { return cs_abi_version(); }
 
 // ---- QMIX learner: the GRU recurrence over T steps (cs_gru_seq_forward / cs_gru_seq_backward) ------------------------------
@@ -769,6 +799,8 @@ TORCH_LIBRARY(coopsearch, m) {
           "Tensor(a!)[] outs) -> ()", &store_episodes_compact);
     m.def("render_episodes(Tensor states, Tensor? maps, Tensor counts, int n_agents, int n_targets, int side, int size, int[] radii, "
           "int layers, int[] colours, Tensor palette, Tensor lut, Tensor(a!) frames) -> ()", &render_episodes);
+    m.def("coverage_actions(Tensor state, Tensor(a!) grid, Tensor(b!) actions, int n_agents, int side, int view_range, int keep, "
+          "int regrow, int lookahead) -> ()", &coverage_actions);
     m.def("gru_seq_forward(Tensor w_hh, Tensor b_hh, Tensor gi, Tensor? h0, int T, int rows, Tensor(a!) h_out, "
           "Tensor(b!)? saved_out) -> ()", &gru_seq_forward);
     m.def("gru_seq_backward(Tensor w_hh, Tensor dh_seq, Tensor h_seq, Tensor? h0, Tensor saved, int T, int rows, "

@@ -39,7 +39,7 @@ extern "C" {
                               still 7: cs_gru_seq_forward, cs_gru_seq_backward, cs_learn_last_error were ADDED, then
                               cs_episode_returns, then cs_policy_pack_device, then cs_collect_flight, cs_compact_out and
                               cs_store_episodes_compact, then cs_snapshot_bytes, cs_snapshot and cs_restore, then cs_render_params and
-                              cs_render_episodes, then cs_gae and cs_ppo_loss (no existing export or struct changed: a version-7 caller works unchanged) */
+                              cs_render_episodes, then cs_gae and cs_ppo_loss, then cs_coverage_params and cs_coverage_actions (no existing export or struct changed: a version-7 caller works unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
 #define CS_MAX_MAP 64
@@ -489,6 +489,34 @@ typedef struct cs_render_params {
  * map_width != side * side.  The message is cs_episodes_last_error()'s. */
 int cs_render_episodes(const cs_render_params *p, const float *states_dev, const float *maps_dev, const int32_t *counts_dev,
                        int E, int R, uint8_t *frames_dev, void *stream);
+
+/* ---- greedy coverage baseline: a sweep of a shared belief grid, one launch per decision ------
+ * The reference has no hand-written policy to compare a learner with (policy/trandition.py is a stub with a Random subclass).
+ * This one is the classical answer to cooperative search: every env keeps a belief grid G, int32 [side * side], row-major
+ * [ix * side + iy], in Q16 -- 65536 = "nobody has looked here", the caller fills it with 65536 when an episode starts --; every
+ * call lets G regrow towards 65536, multiplies the cells inside an agent's sensor disc by keep / 65536, and then lets the agents
+ * choose in index order: each takes the action whose look-ahead disc holds the most belief that no earlier agent has claimed.
+ * The policy is DEFINED by baseline.coverage_actions_torch (stock torch ops, integer arithmetic after one quantisation); the
+ * kernel reproduces actions and grid element for element.  It reads only the first 4 n_agents floats of a get_state() row:
+ * agent i = (xn, yn, cos, sin) at 4i; targets, found flags and flight's map are never looked at.
+ *   state_dev    float [B][state_width]     grid_dev  int32 [B][side * side], in / out, values 0..65536 (a cell outside
+ *                                           that range is read as the nearer bound, in the kernel and in the definition)
+ *   actions_dev  int64 [B][n_agents], out: 0 straight, 1 = + pi / 18, 2 = - pi / 18 (the env's coding) */
+typedef struct cs_coverage_params {
+    int32_t n_agents;     /* 1..8 */
+    int32_t side;         /* map_size: cells per side, 1..CS_MAX_MAP */
+    int32_t view_range;   /* sensor radius in cells, 0..CS_MAX_MAP (R = 16 view_range sub-units of 1/16 cell) */
+    int32_t keep;         /* rint((1 - detect_prob) * 65536), 0..65536 */
+    int32_t regrow;       /* every call: G += (65536 - G) >> regrow; 1..16 */
+    int32_t lookahead;    /* distance of the look-ahead point in cells, 0..side */
+    int32_t state_width;  /* floats per state row, >= 4 n_agents */
+    int32_t reserved;     /* must be 0 (CS_E_CONFIG otherwise) */
+} cs_coverage_params;
+
+/* One launch on `stream`, one workgroup per env, no atomics, no synchronisation.  CS_E_CONFIG (before any launch) for a field
+ * out of range, a NULL or misaligned pointer or B < 1.  The message is cs_episodes_last_error()'s. */
+int cs_coverage_actions(const cs_coverage_params *p, const float *state_dev, int B, int32_t *grid_dev, int64_t *actions_dev,
+                        void *stream);
 
 /* ---- QMIX learner: the GRU recurrence of the agent network over T steps, forward and backward ---------------------
  * Replaces the per-transition unroll of policy/qmix.py:160-182 (get_q_values) over network/base_net.py:40-46
