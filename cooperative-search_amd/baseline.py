@@ -68,13 +68,19 @@ def _quant(v, lim):
     return torch.where(r >= -lim, torch.where(r <= lim, r, hi), lo).to(torch.int64)
 
 
+def quantise_positions(state, n_agents, side):
+    """The position part of `quantise`: state rows float32 [B, S] -> (X, Y), int64 [B, n], in sub-units of 1/16 cell."""
+    B, n = int(state.shape[0]), int(n_agents)
+    ag = state[:, :4 * n].reshape(B, n, 4)
+    half = float(side) / 2.0
+    return _quant((ag[..., 0] * half + half) * 16.0, POS_LIM), _quant((ag[..., 1] * half + half) * 16.0, POS_LIM)
+
+
 def quantise(state, n_agents, side):
     """The first 4n floats of state rows float32 [B, S] -> (X, Y, h), int64 [B, n]: positions in sub-units, heading index."""
     B, n = int(state.shape[0]), int(n_agents)
     ag = state[:, :4 * n].reshape(B, n, 4)
-    half = float(side) / 2.0
-    X = _quant((ag[..., 0] * half + half) * 16.0, POS_LIM)
-    Y = _quant((ag[..., 1] * half + half) * 16.0, POS_LIM)
+    X, Y = quantise_positions(state, n, side)
     c, s = _quant(ag[..., 2] * 16384.0, TRIG_LIM), _quant(ag[..., 3] * 16384.0, TRIG_LIM)
     ct, st = (torch.tensor(t, dtype=torch.int64, device=state.device) for t in trig_tables())
     dot = c[..., None] * ct + s[..., None] * st                                           # [B, n, 36]

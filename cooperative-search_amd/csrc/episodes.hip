@@ -153,6 +153,7 @@ __global__ __launch_bounds__(256) void k_compact_small(CompactParams p) {
 
 #include "render.h"   // k_render_episodes: episode rows -> RGB frames (cs_render_episodes)
 #include "coverage.h" // k_coverage_actions: the greedy coverage baseline (cs_coverage_actions)
+#include "sweep.h"    // k_sweep_episodes: swept-area accounting of recorded episodes (cs_sweep_episodes)
 
 thread_local char g_eerr[160] = "";
 
@@ -277,6 +278,33 @@ int cs_coverage_actions(const cs_coverage_params *p, const float *state_dev, int
     hipLaunchKernelGGL(k_coverage_actions, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
     if (hipGetLastError() != hipSuccess) {
         snprintf(g_eerr, sizeof(g_eerr), "cs_coverage_actions: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    return CS_OK;
+}
+
+int cs_sweep_episodes(const cs_sweep_params *p, const float *states_dev, const int32_t *counts_dev, int E, int32_t *first_dev,
+                      int32_t *new_dev, int32_t *seen_dev, void *stream) {
+    const char *bad = nullptr;
+    if (!p || !states_dev || !counts_dev || !first_dev || !new_dev || !seen_dev) bad = "a NULL pointer";
+    else if (E < 1) bad = "E must be >= 1";
+    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
+    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
+    else if (p->view_range < 0 || p->view_range > CS_MAX_MAP) bad = "view_range must be 0..64";
+    else if (p->state_width < 4 * p->n_agents) bad = "state_width must be at least 4 n_agents";
+    else if (p->rows < 1) bad = "rows must be >= 1";
+    else if (p->reserved != 0) bad = "reserved must be 0";
+    else if ((uintptr_t)states_dev % 4 != 0 || (uintptr_t)counts_dev % 4 != 0 || (uintptr_t)first_dev % 4 != 0 ||
+             (uintptr_t)new_dev % 4 != 0 || (uintptr_t)seen_dev % 4 != 0)
+        bad = "a pointer is not aligned to its element size";
+    if (bad) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_sweep_episodes: %s", bad);
+        return CS_E_CONFIG;
+    }
+    const SweepArgs a{states_dev, counts_dev, first_dev, new_dev, seen_dev, p->n_agents, p->side, p->state_width, p->rows, 16 * p->view_range};
+    hipLaunchKernelGGL(k_sweep_episodes, dim3((unsigned)E), dim3(SWEEP_THREADS), 0, (hipStream_t)stream, a);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_sweep_episodes: kernel launch failed");
         return CS_E_LAUNCH;
     }
     return CS_OK;

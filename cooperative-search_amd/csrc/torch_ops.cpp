@@ -638,6 +638,37 @@ void coverage_actions(const Tensor &state, Tensor grid, Tensor actions, int64_t 
     TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
 }
 
+// ---- swept-area accounting (cs_sweep_episodes): states [E, T1, S >= 4n] float32, counts [E] int32, first [E, side * side],
+// new_cells and seen_cells [E, T1] int32 (out).  Integers and shapes first (nothing is dereferenced), then the tensors.
+void sweep_episodes(const Tensor &states, const Tensor &counts, Tensor first, Tensor new_cells, Tensor seen_cells, int64_t n_agents,
+                    int64_t side, int64_t view_range) {
+    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: sweep_episodes: n_agents must be 1..8, got ", n_agents);
+    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: sweep_episodes: side must be 1..", CS_MAX_MAP, ", got ", side);
+    TORCH_CHECK(view_range >= 0 && view_range <= CS_MAX_MAP, "coopsearch: sweep_episodes: view_range must be 0..", CS_MAX_MAP, ", got ",
+                view_range);
+    TORCH_CHECK(states.dim() == 3 && states.size(0) >= 1 && states.size(0) <= INT32_MAX && states.size(1) >= 1 &&
+                    states.size(1) <= INT32_MAX && states.size(2) >= 4 * n_agents && states.size(2) <= INT32_MAX,
+                "coopsearch: sweep_episodes: states must be [E, T1, S] with E >= 1, T1 >= 1 and S >= 4 n_agents = ", 4 * n_agents);
+    const int64_t E = states.size(0), T1 = states.size(1), S = states.size(2);
+    TORCH_CHECK(counts.dim() == 1 && counts.size(0) == E, "coopsearch: sweep_episodes: counts must be [", E, "]");
+    TORCH_CHECK(first.dim() == 2 && first.size(0) == E && first.size(1) == side * side, "coopsearch: sweep_episodes: first must be [", E,
+                ", ", side * side, "]");
+    TORCH_CHECK(new_cells.dim() == 2 && new_cells.size(0) == E && new_cells.size(1) == T1,
+                "coopsearch: sweep_episodes: new_cells must be [", E, ", ", T1, "]");
+    TORCH_CHECK(seen_cells.dim() == 2 && seen_cells.size(0) == E && seen_cells.size(1) == T1,
+                "coopsearch: sweep_episodes: seen_cells must be [", E, ", ", T1, "]");
+    TORCH_CHECK(states.is_cuda(), "coopsearch: sweep_episodes: states must be a GPU tensor");
+    check_f32(states, "states", E * T1 * S, states);
+    check_dev(counts, "counts", at::kInt, E, states);
+    check_dev(first, "first", at::kInt, E * side * side, states);
+    check_dev(new_cells, "new_cells", at::kInt, E * T1, states);
+    check_dev(seen_cells, "seen_cells", at::kInt, E * T1, states);
+    const cs_sweep_params p{(int32_t)n_agents, (int32_t)side, (int32_t)view_range, (int32_t)S, (int32_t)T1, 0};
+    const int rc = cs_sweep_episodes(&p, states.data_ptr<float>(), counts.data_ptr<int32_t>(), (int)E, first.data_ptr<int32_t>(),
+                                     new_cells.data_ptr<int32_t>(), seen_cells.data_ptr<int32_t>(), stream_of(states));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
 int64_t abi_version() { return cs_abi_version(); }
 
 // ---- QMIX learner: the GRU recurrence over T steps (cs_gru_seq_forward / cs_gru_seq_backward) ------------------------------
@@ -801,6 +832,8 @@ TORCH_LIBRARY(coopsearch, m) {
           "int layers, int[] colours, Tensor palette, Tensor lut, Tensor(a!) frames) -> ()", &render_episodes);
     m.def("coverage_actions(Tensor state, Tensor(a!) grid, Tensor(b!) actions, int n_agents, int side, int view_range, int keep, "
           "int regrow, int lookahead) -> ()", &coverage_actions);
+    m.def("sweep_episodes(Tensor states, Tensor counts, Tensor(a!) first, Tensor(b!) new_cells, Tensor(c!) seen_cells, int n_agents, "
+          "int side, int view_range) -> ()", &sweep_episodes);
     m.def("gru_seq_forward(Tensor w_hh, Tensor b_hh, Tensor gi, Tensor? h0, int T, int rows, Tensor(a!) h_out, "
           "Tensor(b!)? saved_out) -> ()", &gru_seq_forward);
     m.def("gru_seq_backward(Tensor w_hh, Tensor dh_seq, Tensor h_seq, Tensor? h0, Tensor saved, int T, int rows, "

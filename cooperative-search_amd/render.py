@@ -304,20 +304,20 @@ def render_episodes(states, maps, counts, spec, out=None):
     return out
 
 
-def episode_tables(batch, args=None):
+def episode_tables(batch, args=None, with_maps=True):
     """(states [E, T+1, S], maps [E, T+1, cells] or None, counts int32 [E]) of an episode batch, float32.  A dense batch (the
     reference's 11 keys): row 0 is s[:, 0] and row t + 1 is s_next[:, t]; the map (observations wider than 4 floats) is agent
     0's part of o / o_next.  A map-once batch (replay.COMPACT_KEYS): s_full and map as they are.  counts = real steps + 1,
-    computed where the batch lives (no host read)."""
+    computed where the batch lives (no host read).  with_maps=False: maps is None and no map is copied (sweep.sweep_batch)."""
     f32 = torch.float32
     if "s_full" in batch:
-        states, maps = batch["s_full"].to(f32), batch["map"].to(f32)
+        states, maps = batch["s_full"].to(f32), batch["map"].to(f32) if with_maps else None
     else:
         states = torch.cat([batch["s"][:, :1], batch["s_next"]], 1).to(f32)
         cells = int(batch["o"].shape[-1]) - 4
         if args is not None and bool(getattr(args, "conv", cells > 0)) != (cells > 0):
             raise ValueError(f"episode_tables: observations of {cells + 4} floats do not fit args.conv = {args.conv!r}")
-        maps = torch.cat([batch["o"][:, :1, 0, :cells], batch["o_next"][:, :, 0, :cells]], 1).to(f32) if cells > 0 else None
+        maps = torch.cat([batch["o"][:, :1, 0, :cells], batch["o_next"][:, :, 0, :cells]], 1).to(f32) if cells > 0 and with_maps else None
     counts = ((1 - batch["padded"].to(f32)).sum(1).reshape(-1) + 1).to(torch.int32)
     return states.contiguous(), None if maps is None else maps.contiguous(), counts
 

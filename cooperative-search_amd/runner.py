@@ -25,6 +25,7 @@ from .agents import FusedAgents
 from .collector import EpisodeCollector, EpsilonSchedule
 from .learner import DOPLearner, PPOLearner, QMixLearner, ReinforceLearner
 from .replay import CompactReplayBuffer, DeviceReplayBuffer
+from .sweep import with_sweep_bonus
 
 # fields the reference's get_mixer_args / get_common_args set and this package's get_*_args leave to the caller
 # (common/arguments.py:43-46, :84-104)
@@ -103,7 +104,10 @@ class Runner:
     generate_episodes(compact=True); the schedule of calls is the same.  args.conv_impl (absent: "torch") goes to the learner.
     Exact resume (DESIGN.md section 14): `save_state` / `load_state` carry everything that changes during `run`;
     args.state_cycle (absent or 0: never) writes <model_path>/state.pt every that many epochs, args.load_state=True loads it
-    here.  `epoch` and `train_steps` count what this run has done; `run` goes on from them."""
+    here.  args.sweep_bonus (absent or 0: off, and the learner is handed the very batch object it was before): the reward the
+    learner sees is r + sweep_bonus * (cells the step sweeps for the first time) (sweep.with_sweep_bonus, DESIGN.md section 18);
+    evaluation, episode_rewards, the ring and save_state never see it.  `epoch` and `train_steps` count what this run has done;
+    `run` goes on from them."""
 
     def __init__(self, env, args, learner=None, agents=None, schedule=None, collector=None, buffer=None):
         alg = getattr(args, "alg", None)
@@ -244,7 +248,11 @@ class Runner:
 
     def train(self, batch, train_step):
         """agent.py:112-136: one learn call (QMIX without epsilon, DOP, REINFORCE and PPO with env 0's), the acting network repacked,
-        a checkpoint when train_step > 0 and train_step % save_cycle == 0."""
+        a checkpoint when train_step > 0 and train_step % save_cycle == 0.  With args.sweep_bonus the batch passes through
+        sweep.with_sweep_bonus first."""
+        beta = float(getattr(self.args, "sweep_bonus", 0) or 0)
+        if beta:   # the exploration bonus (sweep.py): a copy of the dict with r + bonus; the batch and the ring stay as they are
+            batch = with_sweep_bonus(batch, self.args, beta)
         if self.args.alg == "qmix":
             self.learner.learn(batch, None, train_step)
         else:

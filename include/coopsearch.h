@@ -39,7 +39,7 @@ extern "C" {
                               still 7: cs_gru_seq_forward, cs_gru_seq_backward, cs_learn_last_error were ADDED, then
                               cs_episode_returns, then cs_policy_pack_device, then cs_collect_flight, cs_compact_out and
                               cs_store_episodes_compact, then cs_snapshot_bytes, cs_snapshot and cs_restore, then cs_render_params and
-                              cs_render_episodes, then cs_gae and cs_ppo_loss, then cs_coverage_params and cs_coverage_actions (no existing export or struct changed: a version-7 caller works unchanged) */
+                              cs_render_episodes, then cs_gae and cs_ppo_loss, then cs_coverage_params and cs_coverage_actions, then cs_sweep_params and cs_sweep_episodes (no existing export or struct changed: a version-7 caller works unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
 #define CS_MAX_MAP 64
@@ -517,6 +517,34 @@ typedef struct cs_coverage_params {
  * out of range, a NULL or misaligned pointer or B < 1.  The message is cs_episodes_last_error()'s. */
 int cs_coverage_actions(const cs_coverage_params *p, const float *state_dev, int B, int32_t *grid_dev, int64_t *actions_dev,
                         void *stream);
+
+/* ---- swept-area accounting of recorded episodes, one launch per episode batch ---------------
+ * How much of the map a team's sensors have swept by row t of an episode, and how much of a row's sweeping lands on ground
+ * already seen: the measure of HOW a policy searches, beside the found-fraction curve, and -- as its per-step increment -- a
+ * count-based exploration bonus.  Rows are get_state() rows as render's tables hold them (row 0: the reset pose, row t + 1:
+ * after step t); only the first 4 n_agents floats of a row are read: agent i = (xn, yn, cos, sin) at 4i.  Positions are
+ * quantised as cs_coverage_actions quantises them and a cell is swept at a row when its centre lies within 16 view_range
+ * sub-units of any agent (the sweep test of the coverage policy).  DEFINED by sweep.sweep_episodes_torch (stock torch ops,
+ * integer after one quantisation); the kernel reproduces the three outputs element for element.
+ *   states_dev  float [E][rows][state_width]     counts_dev  int32 [E]: row t of episode e is valid if t < clamp(counts[e], 0, rows);
+ *                                                a row at or past the count is never read
+ *   first_dev   int32 [E][side * side], out: the first valid row at which the cell (ix * side + iy) is swept, -1 if never
+ *   new_dev     int32 [E][rows], out: the number of cells with first == t        (0 at and past the count)
+ *   seen_dev    int32 [E][rows], out: the number of cells swept at row t         (0 at and past the count) */
+typedef struct cs_sweep_params {
+    int32_t n_agents;     /* 1..8 */
+    int32_t side;         /* map_size: cells per side, 1..CS_MAX_MAP */
+    int32_t view_range;   /* sensor radius in cells, 0..CS_MAX_MAP */
+    int32_t state_width;  /* floats per state row, >= 4 n_agents */
+    int32_t rows;         /* rows per episode (T + 1), >= 1 */
+    int32_t reserved;     /* must be 0 (CS_E_CONFIG otherwise) */
+} cs_sweep_params;
+
+/* One launch on `stream`, one workgroup per episode, no atomics, no synchronisation; every element of the three outputs is
+ * written.  CS_E_CONFIG (before any launch) for a field out of range, a NULL or misaligned pointer or E < 1.  The message is
+ * cs_episodes_last_error()'s. */
+int cs_sweep_episodes(const cs_sweep_params *p, const float *states_dev, const int32_t *counts_dev, int E, int32_t *first_dev,
+                      int32_t *new_dev, int32_t *seen_dev, void *stream);
 
 /* ---- QMIX learner: the GRU recurrence of the agent network over T steps, forward and backward ---------------------
  * Replaces the per-transition unroll of policy/qmix.py:160-182 (get_q_values) over network/base_net.py:40-46
