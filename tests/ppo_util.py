@@ -65,12 +65,28 @@ EPSILONS, BETAS = (0.0, 0.3), (0.0, 0.01)
 UNAVAILABLE = (5, 13, 3)
 SEED = 0
 A = 3
+# The other row widths k_ppo_loss<A> is instantiated for (ppo_launch, csrc/policy.hip: 2 .. 8): the smallest, the two next to the
+# tested 3, the largest; on a partial block and on several wavefronts, with the entropy term on.  loss_case's conditions depend on
+# the draw, so every (A, shape, epsilon) has its own seed: the smallest one for which they hold, found on the CPU
+# (test_learner_ppo_cpu.test_loss_twin_in_float32_matches_float64_at_every_width checks them again).  With A = 2 the rows that lose
+# an action keep one: p = 1, entropy 0, log p = 0 -- the edge of the kernel's p_a > 0 guards.
+WIDTHS = (2, 4, 5, 8)
+WIDTH_SHAPES = [(3, 5, 3), (5, 13, 3)]
+WIDTH_BETA = 0.01
+WIDTH_SEEDS = {   # (A, (E, T, n), epsilon): seed
+    (2, (3, 5, 3), 0.0): 1, (2, (3, 5, 3), 0.3): 2, (2, (5, 13, 3), 0.0): 0, (2, (5, 13, 3), 0.3): 19,
+    (4, (3, 5, 3), 0.0): 0, (4, (3, 5, 3), 0.3): 1, (4, (5, 13, 3), 0.0): 0, (4, (5, 13, 3), 0.3): 0,
+    (5, (3, 5, 3), 0.0): 0, (5, (3, 5, 3), 0.3): 2, (5, (5, 13, 3), 0.0): 1, (5, (5, 13, 3), 0.3): 0,
+    (8, (3, 5, 3), 0.0): 1, (8, (3, 5, 3), 0.3): 1, (8, (5, 13, 3), 0.0): 0, (8, (5, 13, 3), 0.3): 0,
+}
+WIDTH_CASES = [(A_, E, T, n, eps) for A_ in WIDTHS for (E, T, n) in WIDTH_SHAPES for eps in EPSILONS]
 
 
-def loss_inputs(E, T, n, unavailable, seed):
+def loss_inputs(E, T, n, unavailable, seed, A=A):
     """float64 CPU tensors of one case: logits ~ N(0, 1.5); episodes of random length (padded rows: avail all zero, garbage
     logits / old_logp / adv); `unavailable`: a third of the live rows lose one action other than the one taken; old_logp: the
-    log-probability of u under logits perturbed by N(0, 0.6) (filled in by loss_case, which knows epsilon)."""
+    log-probability of u under logits perturbed by N(0, 0.6) (filled in by loss_case, which knows epsilon).  A: the row width
+    (with A = 3 the draws are the ones the existing cases have always had)."""
     rng = np.random.RandomState(1000 + seed)
     logits = rng.randn(E, T, n, A) * 1.5
     lengths = rng.randint(1, T + 1, size=E)
@@ -103,14 +119,17 @@ def twin(x, dtype, epsilon, beta):
     return loss.detach().double(), stats.double(), logits.grad.double(), int(round(float(stats[2]) * live_rows))
 
 
-def loss_case(E, T, n, epsilon, beta):
-    """One case (LOSS_SHAPES x EPSILONS x BETAS) with its float64 yardstick, after asserting from that yardstick that (a) each of
+def loss_case(E, T, n, epsilon, beta, A=A, seed=None):
+    """One case (LOSS_SHAPES x EPSILONS x BETAS at A = 3, seed SEED; WIDTH_CASES at WIDTH_BETA with the seed WIDTH_SEEDS names;
+    `seed` overrides either: the search for those seeds) with its float64 yardstick, after asserting from that yardstick that (a) each of
     the four classes (advantage sign x ratio inside / outside the clip range) holds at least 10 % of the live rows (the one-row case
     is exempt) and (b) no live row's ratio lies within 1e-4 of 1 +- CLIP: float32 then decides every row's branch as float64
     does and no row needs to be left out."""
     from cooperative_search_amd.learner import action_prob, log_pi_taken
-    unavailable, seed = (E, T, n) == UNAVAILABLE, SEED
-    x = loss_inputs(E, T, n, unavailable, seed)
+    unavailable = (E, T, n) == UNAVAILABLE
+    if seed is None:
+        seed = SEED if A == 3 else WIDTH_SEEDS[(A, (E, T, n), epsilon)]
+    x = loss_inputs(E, T, n, unavailable, seed, A)
     m3 = x["mask"].reshape(E, T, 1).expand(E, T, n)
     old = log_pi_taken(action_prob(x["logits"] + x["noise"], x["avail"], epsilon), x["u"], m3)
     x["old_logp"] = torch.where(m3 > 0, old, x["garbage"])

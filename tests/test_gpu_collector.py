@@ -125,6 +125,86 @@ def test_episode_assembly_kernel_equals_torch_definition(T, B, n, w, S):
         assert (ring[k][untouched] == -7.0).all()
 
 
+def off_boundary(shape, device="cuda"):
+    """A contiguous float32 tensor of `shape` that starts one float into an allocation: 4 bytes past a 16-byte boundary."""
+    numel = int(np.prod(shape))
+    base = torch.zeros(numel + 4, device=device)
+    view = base[1:1 + numel].view(shape)
+    assert view.data_ptr() % 16 == 4 and view.is_contiguous()
+    return view
+
+
+def t_chunks(B, rows):
+    """cs_store_episodes' own rule (csrc/episodes.hip): the time rows of an env are split until B * chunks reaches 2048 blocks."""
+    chunks = 1
+    while B * chunks < 2048 and chunks < rows:
+        chunks *= 2
+    return chunks
+
+
+def assert_all_kinds_of_episode(term):
+    """term [T, B]: some episode terminates at its first step, some in the middle, some never."""
+    first = term.to(torch.int64).argmax(0)
+    ended = term.any(0)
+    T = term.shape[0]
+    assert bool((ended & (first == 0)).any()) and bool((ended & (first > 0) & (first < T - 1)).any()) and bool((~ended).any())
+
+
+# (T, B, n, w, S, what) -- each case takes a branch the host picks from a shape or a pointer (cs_store_episodes):
+#   vec4 = n * w % 4 == 0 and o_tab, out->o, out->o_next on 16-byte boundaries, else k_episode_rows<1>; chunks as t_chunks
+BRANCH_CASES = [
+    (20, 7, 3, 5, 57, "width"),          # n * w = 15: the first clause fails
+    (20, 7, 3, 4, 57, "o_tab"),          # n * w = 12, the table 4 bytes off: the second clause fails
+    (20, 7, 3, 4, 57, "o"),              # ... the destination of o: the third
+    (20, 7, 3, 4, 57, "o_next"),         # ... the destination of o_next: the fourth
+    (3, 2053, 3, 4, 57, "unsplit"),      # B >= 2048: chunks == 1, one block per env walks all of T (k_episode_rows<4>)
+]
+
+
+@pytest.mark.parametrize("T,B,n,w,S,what", BRANCH_CASES, ids=[c[-1] for c in BRANCH_CASES])
+def test_episode_assembly_scalar_copies_and_unsplit_grid(T, B, n, w, S, what):
+    """k_episode_rows<1> (every clause of the host's vec4 rule, one at a time) and the chunks == 1 grid against the stock-torch
+    statement, into scattered slots of a larger ring whose other slots keep their fill."""
+    from cooperative_search_amd.collector import assemble_episodes, assemble_episodes_torch
+    g = torch.Generator(device="cuda").manual_seed(T * 1000 + B)
+    o = torch.rand(T + 1, B, n, w, device="cuda", generator=g)
+    s = torch.rand(T + 1, B, S, device="cuda", generator=g)
+    u = torch.randint(0, 3, (T, B, n), device="cuda", generator=g)
+    r = torch.randint(-3, 111, (T, B), device="cuda", generator=g).float()
+    end = torch.randint(1, T + 5, (B,), device="cuda", generator=g)           # some episodes never terminate
+    end[:3] = torch.tensor([1, T + 2, T // 2 + 1], device="cuda")             # at the first step, never, in the middle
+    term = (torch.arange(T, device="cuda")[:, None] >= (end - 1)[None, :])   # monotone, like a frozen env
+    assert_all_kinds_of_episode(term)
+    if what == "o_tab":
+        o = off_boundary(o.shape).copy_(o)
+    b = assemble_episodes_torch(o, s, u, r, term, 3)
+    ring = {k: torch.full((B + 3,) + tuple(v.shape[1:]), -7.0, device="cuda") for k, v in b.items()}
+    if what in ("o", "o_next"):
+        ring[what] = off_boundary(ring[what].shape).fill_(-7.0)
+    # the branch, by the host's own rule
+    aligned = [t.data_ptr() % 16 == 0 for t in (o, ring["o"], ring["o_next"])]
+    if what == "width":
+        assert (n * w) % 4 != 0 and all(aligned)
+    elif what == "unsplit":
+        assert B >= 2048 and t_chunks(B, T) == 1 and (n * w) % 4 == 0 and all(aligned)
+    else:
+        assert (n * w) % 4 == 0 and aligned == [what != k for k in ("o_tab", "o", "o_next")]
+        assert (o if what == "o_tab" else ring[what]).data_ptr() % 16 != 0
+    if what != "unsplit":
+        assert t_chunks(B, T) > 1
+    if what in ("width", "o_tab", "unsplit"):   # fresh destinations are torch allocations: aligned
+        a = assemble_episodes(o, s, u, r, term, 3)
+        for k in b:
+            assert a[k].shape == b[k].shape and torch.equal(a[k], b[k]), k
+    slots = torch.randperm(B + 3, device="cuda", generator=g)[:B]
+    assemble_episodes(o, s, u, r, term, 3, out=ring, slots=slots)
+    untouched = torch.ones(B + 3, dtype=torch.bool, device="cuda")
+    untouched[slots] = False
+    for k in b:
+        assert torch.equal(ring[k][slots], b[k]), k
+        assert (ring[k][untouched] == -7.0).all() and int(untouched.sum()) == 3
+
+
 def test_generate_episodes_straight_into_the_replay_ring():
     args = cs.make_env_args("flight_easy", n_agents=3)
     B = 48

@@ -125,6 +125,71 @@ def test_store_episodes_compact_equals_the_torch_definition(T, B, n):
         assert (ring[k][untouched] == -7.0).all() and int(untouched.sum()) == 3
 
 
+def tables_of(lengths, T, n, cells, seed):
+    """test_compact_cpu.tables for any map width: (m, s, o, u, r, term) on the device."""
+    g = torch.Generator().manual_seed(seed)
+    B, S = len(lengths), 4 * n + 45
+    m = torch.rand(T + 1, B, cells, generator=g)
+    s = torch.rand(T + 1, B, S, generator=g) * 2 - 1
+    o = torch.cat([m[:, :, None, :].expand(T + 1, B, n, cells), s[..., :4 * n].reshape(T + 1, B, n, 4)], 3).contiguous()
+    u = torch.randint(0, 3, (T, B, n), generator=g)
+    r = torch.randint(-3, 111, (T, B), generator=g).float()
+    term = torch.arange(T)[:, None] >= (torch.as_tensor(lengths) - 1)[None, :]
+    return tuple(t.cuda() for t in (m, s, o, u, r, term))
+
+
+# (T, B, cells, what) -- each case takes a branch the host picks from a shape or a pointer (cs_store_episodes_compact):
+#   vec4 = cells % 4 == 0 and map_tab, out->map on 16-byte boundaries, else k_compact_rows<1>; the T + 1 rows of an env are
+#   split into chunks until B * chunks reaches 2048 blocks
+COMPACT_BRANCH_CASES = [
+    (9, 5, 2501, "width"),        # cells % 4 == 1: the first clause fails
+    (9, 5, 2500, "map_tab"),      # the table 4 bytes off a 16-byte boundary: the second
+    (9, 5, 2500, "map"),          # the destination: the third
+    (3, 2053, 12, "unsplit"),     # B >= 2048: chunks == 1, one block per env walks all T + 1 rows (k_compact_rows<4>)
+]
+
+
+@pytest.mark.parametrize("T,B,cells,what", COMPACT_BRANCH_CASES, ids=[c[-1] for c in COMPACT_BRANCH_CASES])
+def test_store_episodes_compact_scalar_copies_and_unsplit_grid(T, B, cells, what):
+    """k_compact_rows<1> (every clause of the host's vec4 rule, one at a time) and the chunks == 1 grid against the torch
+    definition, into ring slots that wrap in a ring with room to spare."""
+    from test_gpu_collector import assert_all_kinds_of_episode, off_boundary, t_chunks
+    n = 3
+    lengths = [1, T + 2, T // 2 + 1] + [1 + (7 * j + T) % (T + 3) for j in range(3, B)]   # first step, never, middle; then 1 .. T + 2
+    m, s, o, u, r, term = tables_of(lengths, T, n, cells, seed=T + B)
+    assert_all_kinds_of_episode(term)
+    if what == "map_tab":
+        m = off_boundary(m.shape).copy_(m)
+    want = compact_from_dense(assemble_episodes_torch(o, s, u, r, term, 3))
+    size = B + 3
+    ring = {k: torch.full((size,) + tuple(v.shape[1:]), -7.0, device="cuda") for k, v in want.items()}
+    if what == "map":
+        ring["map"] = off_boundary(ring["map"].shape).fill_(-7.0)
+    # the branch, by the host's own rule
+    aligned = [t.data_ptr() % 16 == 0 for t in (m, ring["map"])]
+    if what == "width":
+        assert cells % 4 != 0 and all(aligned)
+    elif what == "unsplit":
+        assert B >= 2048 and t_chunks(B, T + 1) == 1 and cells % 4 == 0 and all(aligned)
+    else:
+        assert cells % 4 == 0 and aligned == [what != "map_tab", what != "map"]
+        assert (m if what == "map_tab" else ring["map"]).data_ptr() % 16 != 0
+    if what != "unsplit":
+        assert t_chunks(B, T + 1) > 1
+    if what != "map":   # fresh destinations are torch allocations: aligned
+        got = assemble_episodes_compact(m, s, u, r, term)
+        for k in COMPACT_KEYS:
+            assert got[k].shape == want[k].shape and torch.equal(got[k], want[k]), k
+    slots = (torch.arange(B, device="cuda") * 5 + size - 2) % size   # a permutation of B of the size slots (size % 5 != 0), wrapping
+    assert slots.unique().numel() == B
+    assemble_episodes_compact(m, s, u, r, term, out=ring, slots=slots)
+    untouched = torch.ones(size, dtype=torch.bool, device="cuda")
+    untouched[slots] = False
+    for k in COMPACT_KEYS:
+        assert torch.equal(ring[k][slots], want[k]), k
+        assert (ring[k][untouched] == -7.0).all() and int(untouched.sum()) == 3
+
+
 # ---- the collector -----------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("n", [3, 5])

@@ -36,6 +36,7 @@ LIVE_SHARE = 0.20
 # kernel_err is above the 1e-6 floor: 1.05 (conv2.weight of the 19 200-map case; docstring of test_gradients_against_float64_live)
 K = 2.1
 FLOOR = 1e-6
+TOL = 2e-5   # test_gpu_policy's bar for the forward kernels against float32 torch (the conv features: 5 * TOL)
 
 
 def front_end(seed, dtype=torch.float64):
@@ -133,6 +134,45 @@ def test_forward_is_policy_conv_features_bit_for_bit(layout):
     assert want.std() > 0
     with pytest.raises(ValueError, match="maps"):
         ln.ConvFeatures.apply(maps_dev.clone().requires_grad_(), stride, 257, *[x.clone().requires_grad_() for x in w])
+
+
+def test_forward_over_several_trips_in_both_layouts():
+    """k_conv_features with more maps than blocks can be resident (n_maps > 8 * CU: a CU holds at most 32 wavefronts = 8 blocks
+    of 256 threads, whatever the occupancy), so blocks loop: the vec4 branch prefetches the next map into registers while this
+    one computes, the scalar branch (rows of 2 517 floats: the host's rule `map_stride % 4 != 0`) stages with plain loads, and
+    both store a map's features one iteration late.  `feat` is NaN before every launch: a finite row was written.  The two
+    layouts agree bit for bit with each other and with the same kernel in chunks of at most CU maps (<= resident blocks: one
+    map per block, the loop reduced to its final flush), and with float32 torch to the policy tests' 5 * TOL."""
+    cu = torch.cuda.get_device_properties(0).multi_processor_count
+    n_maps = 8 * cu + 5
+    assert n_maps > 8 * cu   # more than one trip of the persistent grid
+    print(f"{cu} CUs: {n_maps} maps > {8 * cu}, chunks of {cu}")
+    conv, linear = front_end(12, torch.float32)
+    maps = make_maps("mixed", n_maps, 1)
+    w = [p.detach().to(DEV) for p in params(conv, linear)]
+    ops = _lib.torch_ops()
+    aligned, (rows, width) = maps.to(DEV), in_rows(maps, 2504 + 10 + 3)
+    assert aligned.data_ptr() % 16 == 0 and CELLS % 4 == 0   # cs_policy_conv_features' vec4 rule holds ...
+    assert width % 4 != 0                                      # ... and here it does not: the scalar staging branch
+    outs = []
+    for table, stride in ((aligned, CELLS), (rows, width)):
+        whole = torch.full((n_maps, 16), float("nan"), device=DEV)
+        ops.policy_conv_features(*w, table, stride, n_maps, whole)
+        assert torch.isfinite(whole).all(), int((~torch.isfinite(whole)).any(1).nonzero()[0])
+        chunked = torch.full((n_maps, 16), float("nan"), device=DEV)
+        for lo in range(0, n_maps, cu):
+            k = min(cu, n_maps - lo)
+            part = torch.full((k, 16), float("nan"), device=DEV)
+            # (a chunk of the aligned table starts lo * 10 000 bytes in: still on a 16-byte boundary)
+            ops.policy_conv_features(*w, table[lo:], stride, k, part)
+            chunked[lo:lo + k] = part
+        assert torch.equal(whole, chunked), (stride, (whole != chunked).any(1).nonzero().flatten()[:8].tolist())
+        outs.append(whole)
+    assert torch.equal(outs[0], outs[1])
+    with torch.no_grad():
+        want = linear.to(DEV)(conv.to(DEV)(aligned.view(n_maps, 1, 50, 50)).reshape(n_maps, 576))
+    assert want.std() > 0
+    assert torch.allclose(outs[0], want, atol=5 * TOL, rtol=5 * TOL), float((outs[0] - want).abs().max())
 
 
 # ---- gradients, live cases -----------------------------------------------------------------------------------------------------

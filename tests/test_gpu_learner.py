@@ -136,6 +136,74 @@ def test_backward_without_h0_and_bad_arguments():
         ops.gru_seq_forward(w_hh, b_hh, gi[:, :39].contiguous(), None, 5, 40, torch.empty(5, 40, H, device=DEV), None)
 
 
+# k_gru_seq_bwd scales every block of 16 rows by its own power of two (from the block's largest |dH| over all t; m == 0 leaves
+# the scale at 1).  The tests above scale the whole tensor by one factor and judge one norm per tensor, which the largest block
+# dominates; these judge dgi and dh0 -- the kernel's own outputs; dW_hh and db_hh are torch sums across the blocks -- block by
+# block.
+
+def kernel_backward(gi, w_hh, b_hh, h0, dH):
+    """(dgi, dh0) of GRUSequence for dH: the two outputs of the backward kernel that belong to a block's own rows."""
+    lgi, lh0 = gi.clone().requires_grad_(True), h0.clone().requires_grad_(True)
+    GRUSequence.apply(lgi, w_hh, b_hh, lh0).backward(dH)
+    torch.cuda.synchronize()
+    return lgi.grad, lh0.grad
+
+
+def test_backward_scales_every_block_of_rows_on_its_own():
+    """Five blocks whose dH are unit normal draws times 2^-100, 2^-40, 1, 2^40 and 2^100 in ONE launch: each block's dgi and dh0
+    rows to 1e-4 relative Frobenius (the bar of the tests above, per block) of fp64 autograd with the same dH.
+    Measured on an MI355X: dgi 2.3e-7 to 2.7e-7 and dh0 2.2e-7 to 3.3e-7 in every block, whatever its exponent."""
+    R, T = 80, 7
+    gi, w_hh, b_hh, h0 = inputs("easy3_qmix", R, T, seed=83)
+    exps = (-100, -40, 0, 40, 100)
+    assert R == 16 * len(exps)
+    factor = torch.tensor([2.0 ** k for k in exps], dtype=torch.float64).repeat_interleave(16)[None, :, None]
+    dH64 = (torch.randn(T, R, H, generator=torch.Generator().manual_seed(84), dtype=torch.float64) * factor).to(DEV)
+    dH = dH64.float()
+    assert torch.isfinite(dH).all() and all(dH[:, 16 * b:16 * b + 16].any() for b in range(len(exps)))   # float32 holds 2^+-100
+    dgi, dh0 = kernel_backward(gi, w_hh, b_hh, h0, dH)
+    leaves = [t.double().requires_grad_(True) for t in (gi, w_hh, b_hh, h0)]
+    gru_fp64(*leaves).backward(dH.double())   # the same dH: float32 -> float64 is exact
+    want_dgi, want_dh0 = leaves[0].grad, leaves[3].grad
+    assert torch.isfinite(dgi).all() and torch.isfinite(dh0).all()
+    errs = []
+    for b, k in enumerate(exps):
+        rows = slice(16 * b, 16 * b + 16)
+        assert float(want_dgi[:, rows].norm()) > 0 and float(want_dh0[rows].norm()) > 0
+        errs.append((k, rel(dgi[:, rows], want_dgi[:, rows]), rel(dh0[rows], want_dh0[rows])))
+    print("gru backward, per block (exponent, dgi, dh0):", ", ".join(f"(2^{k}: {a:.2e}, {c:.2e})" for k, a, c in errs))
+    for k, a, c in errs:
+        assert a <= 1e-4 and c <= 1e-4, (k, a, c)
+
+
+def test_backward_of_an_all_zero_block_is_zero_and_leaves_its_neighbours_alone():
+    """R = 40 (blocks of 16, 16 and 8 rows), dH of rows 16..31 zero at every t: that block's dgi and dh0 are exactly zero (the
+    m == 0 path: scale 1), and the other two blocks are bit-identical to a launch in which rows 16..31 carry dH of their own --
+    no block reads another's rows."""
+    R, T = 40, 5
+    gi, w_hh, b_hh, h0 = inputs("easy3_qmix", R, T, seed=85)
+    dH = torch.randn(T, R, H, generator=torch.Generator().manual_seed(86)).to(DEV)
+    holed = dH.clone()
+    holed[:, 16:32] = 0.0
+    dgi_full, dh0_full = kernel_backward(gi, w_hh, b_hh, h0, dH)
+    dgi, dh0 = kernel_backward(gi, w_hh, b_hh, h0, holed)
+    assert not dgi[:, 16:32].any() and not dh0[16:32].any()
+    assert dgi_full[:, 16:32].any() and dh0_full[16:32].any()
+    for rows in (slice(0, 16), slice(32, 40)):
+        assert torch.equal(dgi[:, rows], dgi_full[:, rows]) and torch.equal(dh0[rows], dh0_full[rows])
+        assert dgi[:, rows].any() and dh0[rows].any()
+
+
+def test_backward_of_all_zero_dH_is_all_zero():
+    """A whole launch of zeros (R = 15: one partial block): every gradient is zero and finite, nothing divides by the block's m."""
+    R, T = 15, 5
+    gi, w_hh, b_hh, h0 = inputs("easy3_qmix", R, T, seed=87)
+    leaves = [t.clone().requires_grad_(True) for t in (gi, w_hh, b_hh, h0)]
+    GRUSequence.apply(*leaves).backward(torch.zeros(T, R, H, device=DEV))
+    for name, leaf in zip(("dgi", "dW_hh", "db_hh", "dh0"), leaves):
+        assert torch.isfinite(leaf.grad).all() and not leaf.grad.any(), name
+
+
 # ---- the fused learner ------------------------------------------------------------------------------------------------------
 
 @pytest.fixture(scope="module")

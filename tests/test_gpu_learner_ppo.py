@@ -11,7 +11,8 @@ import torch
 import cooperative_search_amd as cs
 from cooperative_search_amd import runner as rn
 from cooperative_search_amd.learner import PPOLearner, PPOPolicyLoss, episode_returns, gae, get_ppo_args, ppo_logp
-from ppo_util import BETAS, CLIP, EPSILONS, LOSS_SHAPES, gae_case, gae_f32, gae_f64, loss_case, rel_err, twin
+from ppo_util import (BETAS, CLIP, EPSILONS, LOSS_SHAPES, WIDTH_BETA, WIDTH_CASES, gae_case, gae_f32, gae_f64, loss_case, rel_err,
+                      twin)
 from test_gpu_learner_pg import acts_with, first_step_q, no_sync, replay, to_dev
 from test_gpu_resume import flat
 from test_learner_ppo_cpu import check_reinforce_identity
@@ -74,14 +75,31 @@ def kernel_loss(x, epsilon, beta, eps_on_device=False):
 @pytest.mark.parametrize("epsilon", EPSILONS)
 @pytest.mark.parametrize("beta", BETAS)
 def test_ppo_loss_kernel_matches_float64_autograd(E, T, n, epsilon, beta):
-    x = loss_case(E, T, n, epsilon, beta)   # asserts the conditions on the case from the float64 yardstick
+    check_ppo_loss_kernel(E, T, n, epsilon, beta, 3)
+
+
+@pytest.mark.parametrize("A,E,T,n,epsilon", WIDTH_CASES)
+def test_ppo_loss_kernel_matches_float64_autograd_at_every_width(A, E, T, n, epsilon):
+    """k_ppo_loss<A> for the widths ppo_launch instantiates besides 3 (2, 4, 5 and 8 of 2 .. 8), under the bar of the test above,
+    unchanged: max(1e-6, K * twin error), K = 6.5, both errors against the float64 twin.  With A = 2 the rows of the (5, 13, 3)
+    shape that lose an action keep a single one: p = 1, entropy 0, log p = 0.
+    Measured on an MI355X over the 16 cases: dlogits kernel 9.3e-8 to 3.7e-7 from float64, twin 6.6e-8 to 3.6e-7, ratio 0.74 to
+    2.96 (worst: A = 8, E, T, n = 3, 5, 3, epsilon 0); stats kernel 2.3e-8 to 2.0e-7, twin 1.6e-8 to 2.2e-7, ratio 0.53 to 4.16
+    (worst: A = 8, E, T, n = 5, 13, 3, epsilon 0.3, kernel 1.0e-7 against a twin of 2.5e-8).  Every error lies under the 1e-6
+    floor, which binds here as it does for A = 3; per width the worst dlogits error is 2.6e-7 (A = 2), 3.7e-7 (4), 2.7e-7 (5),
+    2.7e-7 (8)."""
+    check_ppo_loss_kernel(E, T, n, epsilon, WIDTH_BETA, A)
+
+
+def check_ppo_loss_kernel(E, T, n, epsilon, beta, A):
+    x = loss_case(E, T, n, epsilon, beta, A)   # asserts the conditions on the case from the float64 yardstick
     loss64, stats64, d64, count64 = x["want"]
     loss32, stats32, d32, _ = twin(x, torch.float32, epsilon, beta)
     loss, stats, d, logp = kernel_loss(x, epsilon, beta, eps_on_device=epsilon > 0)
     vec = lambda l, s: torch.cat([s[:2].double(), s[3:].double(), l.reshape(1).double()])   # policy loss, entropy, KL, loss
     err_d, twin_d = rel_err(d, d64), rel_err(d32, d64)
     err_s, twin_s = rel_err(vec(loss, stats), vec(loss64, stats64)), rel_err(vec(loss32, stats32), vec(loss64, stats64))
-    print(f"ppo_loss E={E} T={T} n={n} eps={epsilon} beta={beta}: dlogits kernel {err_d:.3g} twin {twin_d:.3g} ratio "
+    print(f"ppo_loss A={A} E={E} T={T} n={n} eps={epsilon} beta={beta}: dlogits kernel {err_d:.3g} twin {twin_d:.3g} ratio "
           f"{err_d / max(twin_d, 1e-30):.3g}; stats kernel {err_s:.3g} twin {twin_s:.3g} ratio {err_s / max(twin_s, 1e-30):.3g}")
     assert err_d <= max(1e-6, K * twin_d)
     assert err_s <= max(1e-6, K * twin_s)
@@ -98,8 +116,8 @@ def test_ppo_loss_kernel_matches_float64_autograd(E, T, n, epsilon, beta):
     c = lambda k, *shape: x[k].float().to(DEV).reshape(*shape).contiguous()
     R = E * T * n
     full_logp, scratch = torch.empty(R, device=DEV), torch.empty(4 * ((R + 255) // 256), device=DEV)
-    ops.ppo_loss(c("logits", R, 3), c("avail", R, 3), x["u"].to(DEV).reshape(R), c("old_logp", R), c("adv", E * T), c("mask", E * T),
-                 R, n, 3, CLIP, beta, epsilon, None, (1 / (n * c("mask", E * T).sum())).reshape(1), torch.empty(R, 3, device=DEV),
+    ops.ppo_loss(c("logits", R, A), c("avail", R, A), x["u"].to(DEV).reshape(R), c("old_logp", R), c("adv", E * T), c("mask", E * T),
+                 R, n, A, CLIP, beta, epsilon, None, (1 / (n * c("mask", E * T).sum())).reshape(1), torch.empty(R, A, device=DEV),
                  full_logp, torch.empty(4, device=DEV), scratch)
     assert torch.equal(full_logp.cpu().view(torch.int32), logp.reshape(R).view(torch.int32))
     live = (x["mask"] > 0).reshape(E, T, 1).expand(E, T, n)

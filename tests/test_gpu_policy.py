@@ -235,6 +235,156 @@ def test_flight_fused_forward_matches_torch_module(n, B):
         last = torch.nn.functional.one_hot(act, 3).float()
 
 
+# ---- the persistent grids beyond one trip (cs_policy_forward / cs_policy_conv_features: grid = min(work, resident blocks)) ----
+# A CU holds at most 32 wavefronts = 8 blocks of 256 threads, whatever occupancy the runtime reports for a kernel: more than
+# 8 * CU tiles (maps) cannot be resident at once, so some block takes a second trip through its loop -- the prefetch hand-over
+# (hv = nhv), wavefront 0 still selecting while the others stage the next tile, the late store of a map's features.  At most
+# 16 * CU rows (CU maps) fit one trip for certain: a launch of that size is the single-trip statement of the same arithmetic.
+
+def _cu():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def _several_trips_batch(n):
+    """Envs of n agents whose rows fill more than 8 * CU tiles and leave a ragged last one."""
+    B = 16 * 8 * _cu() // n + 1
+    while (B * n) % 16 == 0:
+        B += 1
+    rows = B * n
+    assert (rows + 15) // 16 > 8 * _cu() and rows > 16 * 8 * _cu() and rows % 16 != 0   # more than one trip, whatever the occupancy
+    print(f"{_cu()} CUs: {B} envs x {n} agents = {rows} rows = {(rows + 15) // 16} tiles > {8 * _cu()}")
+    return B
+
+
+def _steps(agents, obs_steps, lo, hi, **kw):
+    """choose_action on envs lo..hi of every step's observations -> [(q, hidden, actions, feat)] as they were after each step."""
+    out = []
+    for obs in obs_steps:
+        act = agents.choose_action(obs[lo:hi], want_q=True, **{k: (v[lo:hi] if torch.is_tensor(v) else v) for k, v in kw.items()})
+        out.append((agents.q.clone(), agents.hidden.clone(), act.clone(), agents.feat.clone() if agents.conv else None))
+    return out
+
+
+def _assert_equals_single_trip_shards(a, net, B, E, obs_steps, whole, seed, **kw):
+    """The same envs through shards of E envs, each a single-trip launch keyed on its global rows: bit for bit what the one
+    launch over all of them left, step by step."""
+    n = a.n_agents
+    for lo in range(0, B, E):
+        hi = min(B, lo + E)
+        part = _steps(FusedAgents(a, hi - lo, net=net, seed=seed, env_offset=lo), obs_steps, lo, hi, **kw)
+        for t, ((q, h, act, feat), (wq, wh, wact, wfeat)) in enumerate(zip(part, whole)):
+            assert torch.equal(q, wq[lo:hi]), (lo, t, "q")
+            assert torch.equal(h, wh[lo * n:hi * n]), (lo, t, "hidden")
+            assert torch.equal(act, wact[lo:hi]), (lo, t, "actions")
+            if feat is not None:
+                assert torch.equal(feat, wfeat[lo:hi]), (lo, t, "feat")
+
+
+def test_fused_forward_over_several_trips_matches_torch_module():
+    """k_policy_h with more tiles than the device can hold (tiles > 8 * CU) and a ragged last tile, two steps (the second from
+    a non-zero hidden state): every row to the bars of test_fused_forward_matches_torch_module."""
+    n = 3
+    B = _several_trips_batch(n)
+    torch.manual_seed(41)
+    a = _args(n)
+    net = AgentRNN(rnn_input_shape(a), a).cuda()
+    for p in net.parameters():
+        p.data.mul_(3.0)
+    fused = FusedAgents(a, B, net=net)
+    ref = BatchedAgents(a, B, net=net)
+    last = torch.zeros(B, n, a.n_actions, device="cuda")
+    for t in range(2):
+        obs = torch.rand(B, n, 4, device="cuda") * 2 - 0.5
+        act = fused.choose_action(obs, want_q=True).clone()
+        x = torch.cat([obs, last, ref.agent_ids], 2).reshape(B * n, -1)
+        with torch.no_grad():
+            q_ref, ref.hidden = net(x, ref.hidden)
+        q_ref = q_ref.reshape(B, n, -1)
+        assert torch.allclose(fused.q, q_ref, atol=TOL, rtol=TOL), (t, (fused.q - q_ref).abs().max().item())
+        assert torch.allclose(fused.hidden, ref.hidden, atol=TOL, rtol=TOL), (t, (fused.hidden - ref.hidden).abs().max().item())
+        top2 = q_ref.topk(2, dim=2).values
+        clear = (top2[..., 0] - top2[..., 1]) > 1e-3
+        assert clear.float().mean().item() > 0.9 and (act == q_ref.argmax(2))[clear].all()
+        ref.hidden = fused.hidden.clone()
+        last = torch.nn.functional.one_hot(act, a.n_actions).float()
+    assert fused.hidden.abs().max().item() > 0.1
+
+
+@pytest.mark.parametrize("rule", ["greedy", "epsilon", "epsilon_per_env", "softmax"])
+def test_one_launch_over_several_trips_equals_single_trip_launches(rule):
+    """A row's arithmetic and its noise do not depend on the tile it lands in or on the trip that tile is computed in: q, hidden
+    state and actions of ONE launch over tiles > 8 * CU equal, bit for bit, those of shards of at most 16 * CU rows (one trip
+    each), under every selection rule; the exploring rules do move actions away from the greedy ones."""
+    n = 3
+    B, cu = _several_trips_batch(n), _cu()
+    E = 16 * cu // n
+    assert n * E <= 16 * cu   # a shard's tiles <= CU <= resident blocks: a single trip
+    a = _args(n)
+    if rule == "softmax":
+        a.alg = "reinforce"
+    torch.manual_seed(43)
+    net = AgentRNN(rnn_input_shape(a), a).cuda()
+    for p in net.parameters():
+        p.data.mul_(3.0)
+    obs_steps = [torch.rand(B, n, 4, device="cuda") * 2 - 0.5 for _ in range(2)]
+    kw = {"greedy": dict(evaluate=True), "epsilon": dict(epsilon=0.3), "softmax": dict(epsilon=0.25),
+          "epsilon_per_env": dict(epsilon=0.9, eps_env=torch.linspace(0.05, 0.95, B, dtype=torch.float64, device="cuda"))}[rule]
+    whole = _steps(FusedAgents(a, B, net=net, seed=77), obs_steps, 0, B, **kw)
+    _assert_equals_single_trip_shards(a, net, B, E, obs_steps, whole, 77, **kw)
+    assert whole[1][1].abs().max().item() > 0.1   # the second step started from a non-zero hidden state
+    if rule != "greedy":
+        greedy = _steps(FusedAgents(a, B, net=net, seed=77), obs_steps[:1], 0, B, evaluate=True)
+        assert torch.equal(greedy[0][0], whole[0][0])          # the same q ...
+        changed = (greedy[0][2] != whole[0][2]).float().mean().item()
+        assert changed > 0.02, changed                          # ... other actions
+        if rule == "epsilon_per_env":   # every env explored with its own epsilon: the last tenth far more often than the first
+            moved = (greedy[0][2] != whole[0][2]).float().mean(1)
+            assert moved[-B // 10:].mean().item() > 3 * moved[:B // 10].mean().item() > 0
+
+
+def test_flight_forward_over_several_trips():
+    """flight with B = 8 * CU + 5 envs: one map per env takes k_conv_features through several trips (n_maps > 8 * CU: the register
+    prefetch of the next map, the features stored one iteration late), and k_policy_h runs with `feat` over 3 B rows.  Features,
+    q and hidden state against the torch module at test_flight_fused_forward_matches_torch_module's bars, and bit for bit
+    against shards of CU envs (one trip of either kernel)."""
+    n, cu = 3, _cu()
+    B, E = 8 * cu + 5, cu
+    assert B > 8 * cu and E <= cu and n * E <= 16 * cu
+    print(f"{cu} CUs: {B} maps > {8 * cu}, {B * n} rows; shards of {E} envs")
+    torch.manual_seed(47)
+    a = _flight_args(n)
+    net = AgentRNN(rnn_input_shape(a), a).cuda()
+    for p in net.parameters():
+        p.data.mul_(2.0)
+    obs_steps = []
+    for t in range(2):
+        maps = torch.rand(B, 1, 2500, device="cuda").expand(B, n, 2500)       # one map per env, as get_obs gives
+        obs_steps.append(torch.cat([maps, torch.rand(B, n, 4, device="cuda")], 2).contiguous())
+    fused = FusedAgents(a, B, net=net, seed=5)
+    ref = BatchedAgents(a, B, net=net)
+    last = torch.zeros(B, n, 3, device="cuda")
+    whole = []
+    for t, obs in enumerate(obs_steps):
+        fused.feat.fill_(float("nan"))   # every env's features are written by this launch, the last map of every block too
+        act = fused.choose_action(obs, want_q=True).clone()
+        whole.append((fused.q.clone(), fused.hidden.clone(), act, fused.feat.clone()))
+        x = torch.cat([obs, last, ref.agent_ids], 2).reshape(B * n, -1)
+        with torch.no_grad():
+            q_ref, ref.hidden = net(x, ref.hidden)
+            f_ref = net.linear(net.conv(obs[:, 0, :2500].reshape(B, 1, 50, 50)).reshape(B, -1))
+        q_ref = q_ref.reshape(B, n, -1)
+        assert torch.isfinite(fused.feat).all()
+        assert torch.allclose(fused.feat, f_ref, atol=5 * TOL, rtol=5 * TOL), (t, (fused.feat - f_ref).abs().max().item())
+        assert torch.allclose(fused.q, q_ref, atol=5 * TOL, rtol=5 * TOL), (t, (fused.q - q_ref).abs().max().item())
+        assert torch.allclose(fused.hidden, ref.hidden, atol=5 * TOL, rtol=5 * TOL)
+        clear = (q_ref.topk(2, dim=2).values.diff(dim=2).abs()[..., 0]) > 1e-3
+        assert (act == q_ref.argmax(2))[clear].all()
+        ref.hidden = fused.hidden.clone()
+        last = torch.nn.functional.one_hot(act, 3).float()
+    del ref, x, q_ref, f_ref
+    _assert_equals_single_trip_shards(a, net, B, E, obs_steps, whole, 5)
+
+
 def test_flight_closed_loop_and_collector_with_fused_agents():
     a = _flight_args(3)
     B = 64

@@ -15,7 +15,8 @@ from cooperative_search_amd import _lib
 from cooperative_search_amd import runner as rn
 from cooperative_search_amd.learner import PPOLearner, ReinforceLearner, ValueCritic, gae_torch, get_ppo_args, returns_torch
 from learn_util import record
-from ppo_util import (BETAS, EPSILONS, LOSS_SHAPES, gae_case, gae_f32, gae_f64, loss_case, ppo_args, rel_err, twin)
+from ppo_util import (BETAS, EPSILONS, LOSS_SHAPES, WIDTH_BETA, WIDTH_CASES, gae_case, gae_f32, gae_f64, loss_case, ppo_args, rel_err,
+                      twin)
 from test_learner_pg_cpu import load_pg_fixture, pg_args
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -129,7 +130,26 @@ def test_reduced_ppo_is_reinforce(fx):
 def test_loss_twin_in_float32_matches_float64(E, T, n, epsilon, beta):
     """The GPU tests' yardstick is sound: float32 autograd of ppo_policy_loss_torch against float64, at float32's precision
     (1e-5 relative: sums of up to ~1000 terms of ~6e-8 each, amplified by the 1 / p of the taken action)."""
-    x = loss_case(E, T, n, epsilon, beta)
+    check_loss_twin(E, T, n, epsilon, beta, 3)
+
+
+@pytest.mark.parametrize("A,E,T,n,epsilon", WIDTH_CASES)
+def test_loss_twin_in_float32_matches_float64_at_every_width(A, E, T, n, epsilon):
+    """The cases of the GPU test of the other row widths (ppo_util.WIDTH_CASES, each with its committed seed): loss_case's
+    conditions hold for every one of them, and the yardstick is sound at that width too.  With A = 2 and unavailable actions
+    some live rows keep a single action: probability 1 and no entropy whatever the logits, so the row's gradient is zero up to
+    float64's rounding of the softmax's backward (a few 1e-18 against entries of 1e-2)."""
+    x = check_loss_twin(E, T, n, epsilon, WIDTH_BETA, A)
+    assert tuple(x["logits"].shape) == (E, T, n, A) and int(x["u"].max()) == A - 1 and int(x["u"].min()) == 0
+    live = (x["mask"] > 0).reshape(E, T, 1).expand(E, T, n)
+    single = (x["avail"].sum(-1) == 1) & live
+    assert bool(single.any()) == (A == 2 and x["unavailable"])
+    if bool(single.any()):
+        assert float(x["want"][2][single].abs().max()) <= 1e-15 and float(x["want"][2].abs().max()) >= 1e-3
+
+
+def check_loss_twin(E, T, n, epsilon, beta, A):
+    x = loss_case(E, T, n, epsilon, beta, A)
     loss64, stats64, d64, count64 = x["want"]
     loss32, stats32, d32, count32 = twin(x, torch.float32, epsilon, beta)
     assert bool(torch.isfinite(d64).all()) and float(d64.norm()) > 0
@@ -138,6 +158,7 @@ def test_loss_twin_in_float32_matches_float64(E, T, n, epsilon, beta):
     assert count32 == count64
     dead = (x["mask"] == 0).reshape(E, T, 1, 1).expand_as(d64)
     assert bool((d64[dead] == 0).all()) and bool((d32[dead] == 0).all())   # padded rows: exactly zero
+    return x
 
 
 def small_ppo(tmp_path, fx, **over):
