@@ -23,6 +23,9 @@
 
 #include "coopsearch.h"
 
+// episodes.hip: sets the message cs_episodes_last_error() returns (cs_move_targets reports there, as cs_sweep_episodes does)
+extern "C" __attribute__((visibility("hidden"))) void episodes_set_error(const char *msg);
+
 namespace {
 
 #include "policy_dev.h"
@@ -1580,6 +1583,7 @@ __global__ __launch_bounds__(BLOCK) void k_emit(DevParams p, float *obs, float *
 
 #include "flight_map.h"
 #include "snapshot.h"   // k_snapshot / k_restore: an env's logical state as one record (cs_snapshot, cs_restore)
+#include "motion.h"     // k_move_targets: one move of every unfound target of every live env (cs_move_targets)
 
 // ---------------------------------------------------------------------------------------------------------
 __global__ void k_seed(DevParams p, const uint32_t *seeds) {
@@ -2440,6 +2444,40 @@ int cs_metrics(const cs_config *cfg, void *state_dev, double *out4_dev, void *st
     if (!out4_dev) return fail(CS_E_ARG, "null metrics buffer");
     hipLaunchKernelGGL(k_metrics, dim3((p.B + 255) / 256), dim3(256), 0, (hipStream_t)stream, p, out4_dev);
     return launched("cs_metrics");
+}
+
+// The message goes to cs_episodes_last_error() (and to cs_last_error(), where a refused cs_config is reported anyway).
+static int motion_fail(int code, const char *msg) {
+    char buf[160];
+    snprintf(buf, sizeof(buf), "cs_move_targets: %s", msg);
+    episodes_set_error(buf);
+    return fail(code, buf);
+}
+
+int cs_move_targets(const cs_config *cfg, void *state_dev, const cs_motion_params *mp, void *stream) {
+    if (check_config(cfg)) return motion_fail(CS_E_CONFIG, g_err);
+    const char *bad = nullptr;
+    if (!mp || !state_dev) bad = "a NULL pointer";
+    else if (mp->mode != CS_MOTION_WALK && mp->mode != CS_MOTION_EVADE) bad = "mode must be 0 (walk) or 1 (evade)";
+    else if (mp->persist < 1 || mp->persist > 65536) bad = "persist must be 1..65536";
+    else if (mp->reserved != 0) bad = "reserved must be 0";
+    else if (!(mp->speed >= 0.0 && mp->speed <= (double)cfg->map_size)) bad = "speed must be finite, 0..map_size";
+    else if (!(mp->sense >= 0.0 && mp->sense <= 2.0 * (double)cfg->map_size)) bad = "sense must be finite, 0..2 map_size";
+    else if (mp->env_offset < 0 || mp->env_offset > (1ll << 62)) bad = "env_offset must be 0..2^62";
+    else if ((reinterpret_cast<size_t>(state_dev) & 15) != 0) bad = "state_dev must be 16-byte aligned";
+    if (bad) return motion_fail(CS_E_CONFIG, bad);
+    if (mp->speed == 0.0) return CS_OK;   // nothing moves: the definition returns its input
+    cs_layout lay;
+    cs_state_layout(cfg, &lay);
+    char *base = static_cast<char *>(state_dev);
+    const MotionArgs a{reinterpret_cast<double *>(base + lay.tgt_off), reinterpret_cast<const double *>(base + lay.agent_off),
+                       reinterpret_cast<const int *>(base + lay.hdr_off), (long long)cfg->batch, (long long)mp->env_offset,
+                       cfg->n_agents, cfg->n_targets, cfg->time_limit, mp->mode, (unsigned)mp->persist, mp->seed,
+                       mp->speed, mp->sense * mp->sense, (double)cfg->map_size};
+    const unsigned blocks = (unsigned)((cfg->batch + MOT_BLOCK / 16 - 1) / (MOT_BLOCK / 16));
+    hipLaunchKernelGGL(k_move_targets, dim3(blocks), dim3(MOT_BLOCK), 0, (hipStream_t)stream, a);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? CS_OK : motion_fail(CS_E_LAUNCH, hipGetErrorString(e));
 }
 
 #ifdef CS_REGION_COUNTS

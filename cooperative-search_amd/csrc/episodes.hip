@@ -312,4 +312,7 @@ int cs_sweep_episodes(const cs_sweep_params *p, const float *states_dev, const i
 
 const char *cs_episodes_last_error(void) { return g_eerr; }
 
+// for coopsearch.hip: cs_move_targets takes a cs_config and the state blob, so it lives there, and reports here
+__attribute__((visibility("hidden"))) void episodes_set_error(const char *msg) { snprintf(g_eerr, sizeof(g_eerr), "%s", msg); }
+
 }  // extern "C"

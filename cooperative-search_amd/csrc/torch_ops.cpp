@@ -669,6 +669,28 @@ void sweep_episodes(const Tensor &states, const Tensor &counts, Tensor first, Te
     TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
 }
 
+// ---- moving targets (cs_move_targets): one move of every unfound target of every live env, in place in the state blob.  mode 0 =
+// walk, 1 = evade (CS_MOTION_*).  The entry point's range checks come first, then the tensor's.
+void move_targets(const Tensor &cfg, Tensor blob, int64_t mode, int64_t persist, int64_t seed, double speed, double sense,
+                  int64_t env_offset) {
+    const cs_config &c = config_of(cfg);
+    cs_layout lay;
+    TORCH_CHECK(cs_state_layout(&c, &lay) == CS_OK, cs_last_error());
+    TORCH_CHECK(mode == CS_MOTION_WALK || mode == CS_MOTION_EVADE, "coopsearch: move_targets: mode must be 0 (walk) or 1 (evade), got ", mode);
+    TORCH_CHECK(persist >= 1 && persist <= 65536, "coopsearch: move_targets: persist must be 1..65536, got ", persist);
+    TORCH_CHECK(seed >= 0 && seed <= 0xffffffffll, "coopsearch: move_targets: seed must be a uint32, got ", seed);
+    TORCH_CHECK(speed >= 0.0 && speed <= (double)c.map_size, "coopsearch: move_targets: speed must be finite, 0..map_size = ", c.map_size,
+                ", got ", speed);
+    TORCH_CHECK(sense >= 0.0 && sense <= 2.0 * (double)c.map_size, "coopsearch: move_targets: sense must be finite, 0..2 map_size = ",
+                2 * c.map_size, ", got ", sense);
+    TORCH_CHECK(env_offset >= 0 && env_offset <= (int64_t(1) << 62), "coopsearch: move_targets: env_offset must be 0..2^62, got ", env_offset);
+    TORCH_CHECK(blob.is_cuda(), "coopsearch: move_targets: blob must be a GPU tensor");
+    check_dev(blob, "blob", at::kByte, (int64_t)lay.total_bytes, blob);
+    const cs_motion_params p{(int32_t)mode, (int32_t)persist, (uint32_t)seed, 0, speed, sense, env_offset};
+    const int rc = cs_move_targets(&c, blob.data_ptr(), &p, stream_of(blob));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
 int64_t abi_version() { return cs_abi_version(); }
 
 // ---- QMIX learner: the GRU recurrence over T steps (cs_gru_seq_forward / cs_gru_seq_backward) ------------------------------
@@ -834,6 +856,8 @@ TORCH_LIBRARY(coopsearch, m) {
           "int regrow, int lookahead) -> ()", &coverage_actions);
     m.def("sweep_episodes(Tensor states, Tensor counts, Tensor(a!) first, Tensor(b!) new_cells, Tensor(c!) seen_cells, int n_agents, "
           "int side, int view_range) -> ()", &sweep_episodes);
+    m.def("move_targets(Tensor cfg, Tensor(a!) blob, int mode, int persist, int seed, float speed, float sense, int env_offset) -> ()",
+          &move_targets);
     m.def("gru_seq_forward(Tensor w_hh, Tensor b_hh, Tensor gi, Tensor? h0, int T, int rows, Tensor(a!) h_out, "
           "Tensor(b!)? saved_out) -> ()", &gru_seq_forward);
     m.def("gru_seq_backward(Tensor w_hh, Tensor dh_seq, Tensor h_seq, Tensor? h0, Tensor saved, int T, int rows, "

@@ -39,7 +39,8 @@ extern "C" {
                               still 7: cs_gru_seq_forward, cs_gru_seq_backward, cs_learn_last_error were ADDED, then
                               cs_episode_returns, then cs_policy_pack_device, then cs_collect_flight, cs_compact_out and
                               cs_store_episodes_compact, then cs_snapshot_bytes, cs_snapshot and cs_restore, then cs_render_params and
-                              cs_render_episodes, then cs_gae and cs_ppo_loss, then cs_coverage_params and cs_coverage_actions, then cs_sweep_params and cs_sweep_episodes (no existing export or struct changed: a version-7 caller works unchanged) */
+                              cs_render_episodes, then cs_gae and cs_ppo_loss, then cs_coverage_params and cs_coverage_actions, then cs_sweep_params and cs_sweep_episodes, then
+                              cs_motion_params and cs_move_targets (no existing export or struct changed: a version-7 caller works unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
 #define CS_MAX_MAP 64
@@ -545,6 +546,42 @@ typedef struct cs_sweep_params {
  * cs_episodes_last_error()'s. */
 int cs_sweep_episodes(const cs_sweep_params *p, const float *states_dev, const int32_t *counts_dev, int E, int32_t *first_dev,
                       int32_t *new_dev, int32_t *seen_dev, void *stream);
+
+/* ---- moving targets: one move of every unfound target of every live env, one launch ----------
+ * The reference's targets never move: tgt is written by cs_reset and only read afterwards, so swept ground never goes stale.
+ * This call is the opt-in scenario in which it does.  Target j < n_targets of env b moves when the env is live on entry --
+ * the predicate by which cs_step with CS_FREEZE_DONE leaves an env alone: win bit of CS_H_FLAGS clear and CS_H_TIME_STEP <
+ * time_limit -- and bit j of CS_H_FOUND is clear.  Every other double of tgt keeps its bits: found targets, slots >=
+ * n_targets, every target of a finished env.  The call reads tgt, agent and hdr and writes tgt, nothing else; nothing else in
+ * the blob is derived from an unfound target's position.  DEFINED by motion.move_targets_torch (stock torch ops, fp64, every
+ * operation rounded once; no sqrt, no division, no transcendental); the kernel reproduces it bit for bit.
+ *   heading  one of 16: CX[k], CY[k] = cos, sin(2 pi k / 16) as doubles (the literals of csrc/motion.h and motion.py)
+ *   walk     k = key >> 28 with, in uint32 arithmetic,
+ *              fmix(x): x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16
+ *              key = seed; for w in (g & 0xffffffff, g >> 32, CS_H_EPISODES, CS_H_TIME_STEP / persist, j): key = fmix(key ^ w) + 0x9E3779B9
+ *            g = env_offset + b, the global env index: a pure function of the env's own logical state and its global index --
+ *            no state of its own, so snapshots and resume need nothing new, a sharded batch equals the whole batch, and one
+ *            state forked into several env indices diffuses differently in each
+ *   evade    d2_i = (x - ax_i)^2 + (y - ay_i)^2 over the agents i < n_agents; if some d2_i <= sense * sense, the nearest such
+ *            agent (lowest i on ties) gives (dx, dy) = (x - ax, y - ay) and k is the lowest index that maximises
+ *            dx CX[k] + dy CY[k]; otherwise k is the walk heading
+ *   move     x' = min(max(x + speed CX[k], 0), map_size), y' likewise with CY
+ * When the moves happen is the caller's business (motion.MovingTargetEnv: before every `every`-th step). */
+enum { CS_MOTION_WALK = 0, CS_MOTION_EVADE = 1 };
+typedef struct cs_motion_params {
+    int32_t mode;         /* CS_MOTION_WALK or CS_MOTION_EVADE */
+    int32_t persist;      /* time steps for which a walk heading is kept: 1..65536 */
+    uint32_t seed;        /* seed of the heading keys */
+    int32_t reserved;     /* must be 0 (CS_E_CONFIG otherwise) */
+    double speed;         /* cells per move: finite, 0..map_size; 0: no launch, nothing moves */
+    double sense;         /* evade: the radius inside which a target sees an agent: finite, 0..2 map_size */
+    int64_t env_offset;   /* global index of env 0, 0..2^62 */
+} cs_motion_params;
+
+/* One launch on `stream` (none when speed is 0), 16 lanes per env, no atomics, no synchronisation.  CS_E_CONFIG (before any
+ * launch) for a cfg that cs_state_layout refuses, a field out of range, a non-zero `reserved`, a NULL pointer or a state_dev
+ * that is not 16-byte aligned.  The message is cs_episodes_last_error()'s (cs_last_error() holds it too). */
+int cs_move_targets(const cs_config *cfg, void *state_dev, const cs_motion_params *p, void *stream);
 
 /* ---- QMIX learner: the GRU recurrence of the agent network over T steps, forward and backward ---------------------
  * Replaces the per-transition unroll of policy/qmix.py:160-182 (get_q_values) over network/base_net.py:40-46
