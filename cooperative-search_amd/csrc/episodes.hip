@@ -154,6 +154,7 @@ __global__ __launch_bounds__(256) void k_compact_small(CompactParams p) {
 #include "render.h"   // k_render_episodes: episode rows -> RGB frames (cs_render_episodes)
 #include "coverage.h" // k_coverage_actions: the greedy coverage baseline (cs_coverage_actions)
 #include "sweep.h"    // k_sweep_episodes: swept-area accounting of recorded episodes (cs_sweep_episodes)
+#include "belief.h"   // k_belief_actions: the target-density filter policy for moving targets (cs_belief_actions)
 
 thread_local char g_eerr[160] = "";
 
@@ -305,6 +306,50 @@ int cs_sweep_episodes(const cs_sweep_params *p, const float *states_dev, const i
     hipLaunchKernelGGL(k_sweep_episodes, dim3((unsigned)E), dim3(SWEEP_THREADS), 0, (hipStream_t)stream, a);
     if (hipGetLastError() != hipSuccess) {
         snprintf(g_eerr, sizeof(g_eerr), "cs_sweep_episodes: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    return CS_OK;
+}
+
+int cs_belief_actions(const cs_belief_params *p, const float *state_dev, int B, int32_t *grid_dev, int32_t *prev_dev,
+                      int64_t *actions_dev, void *stream) {
+    const char *bad = nullptr;
+    if (!p || !state_dev || !grid_dev || !prev_dev || !actions_dev) bad = "a NULL pointer";
+    else if (B < 1) bad = "B must be >= 1";
+    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
+    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
+    else if (p->view_range < 0 || p->view_range > CS_MAX_MAP) bad = "view_range must be 0..64";
+    else if (p->keep < 0 || p->keep > 65536) bad = "keep must be 0..65536";
+    else if (p->lookahead < 0 || p->lookahead > p->side) bad = "lookahead must be 0..side";
+    else if (p->state_width < 4 * p->n_agents) bad = "state_width must be at least 4 n_agents";
+    else if (p->mode != CS_MOTION_WALK && p->mode != CS_MOTION_EVADE) bad = "mode must be CS_MOTION_WALK or CS_MOTION_EVADE";
+    else if (p->moved != 0 && p->moved != 1) bad = "moved must be 0 or 1";
+    else if (p->sense16 < 0 || p->sense16 > 32 * CS_MAX_MAP) bad = "sense16 must be 0..2048";
+    else if (p->reserved != 0) bad = "reserved must be 0";
+    else if ((uintptr_t)grid_dev % 4 != 0 || (uintptr_t)prev_dev % 4 != 0 || (uintptr_t)state_dev % 4 != 0 || (uintptr_t)actions_dev % 8 != 0)
+        bad = "a pointer is not aligned to its element size";
+    for (int k = 0; !bad && k < 16; k++)
+        if (p->dx[k] < -16 * CS_MAX_MAP || p->dx[k] > 16 * CS_MAX_MAP || p->dy[k] < -16 * CS_MAX_MAP || p->dy[k] > 16 * CS_MAX_MAP)
+            bad = "dx and dy must be -1024..1024";
+    if (bad) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_belief_actions: %s", bad);
+        return CS_E_CONFIG;
+    }
+    const int cells = p->side * p->side;
+    BeliefArgs a{};
+    a.c = CoverageArgs{state_dev, grid_dev, actions_dev, p->n_agents, p->side, p->state_width, 16 * p->view_range, p->keep, 16,
+                       16 * p->lookahead, (cells % 4 == 0 && (uintptr_t)grid_dev % 16 == 0) ? 1 : 0};
+    a.prev = prev_dev;
+    a.mode = p->mode;
+    a.moved = p->moved;
+    a.sense2 = (unsigned)p->sense16 * (unsigned)p->sense16;
+    for (int k = 0; k < 16; k++) {
+        a.dx[k] = p->dx[k];
+        a.dy[k] = p->dy[k];
+    }
+    hipLaunchKernelGGL(k_belief_actions, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_belief_actions: kernel launch failed");
         return CS_E_LAUNCH;
     }
     return CS_OK;

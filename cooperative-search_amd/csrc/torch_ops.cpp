@@ -691,6 +691,57 @@ void move_targets(const Tensor &cfg, Tensor blob, int64_t mode, int64_t persist,
     TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
 }
 
+// ---- target-density filter policy (cs_belief_actions): state [B, S >= 4n] float32, grid [B, side * side] int32 and prev [B, 8, 2]
+// int32 (in / out), actions [B, n] int64 (out).  Integers and shapes first (nothing is dereferenced), then the tensors.
+void belief_actions(const Tensor &state, Tensor grid, Tensor prev, Tensor actions, int64_t n_agents, int64_t side, int64_t view_range,
+                    int64_t keep, int64_t lookahead, int64_t mode, int64_t moved, int64_t sense16, at::IntArrayRef dx, at::IntArrayRef dy) {
+    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: belief_actions: n_agents must be 1..8, got ", n_agents);
+    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: belief_actions: side must be 1..", CS_MAX_MAP, ", got ", side);
+    TORCH_CHECK(view_range >= 0 && view_range <= CS_MAX_MAP, "coopsearch: belief_actions: view_range must be 0..", CS_MAX_MAP, ", got ",
+                view_range);
+    TORCH_CHECK(keep >= 0 && keep <= 65536, "coopsearch: belief_actions: keep must be 0..65536, got ", keep);
+    TORCH_CHECK(lookahead >= 0 && lookahead <= side, "coopsearch: belief_actions: lookahead must be 0..side, got ", lookahead);
+    TORCH_CHECK(mode == CS_MOTION_WALK || mode == CS_MOTION_EVADE, "coopsearch: belief_actions: mode must be 0 (walk) or 1 (evade), got ", mode);
+    TORCH_CHECK(moved == 0 || moved == 1, "coopsearch: belief_actions: moved must be 0 or 1, got ", moved);
+    TORCH_CHECK(sense16 >= 0 && sense16 <= 32 * CS_MAX_MAP, "coopsearch: belief_actions: sense16 must be 0..", 32 * CS_MAX_MAP, ", got ", sense16);
+    TORCH_CHECK(dx.size() == 16 && dy.size() == 16, "coopsearch: belief_actions: dx and dy must hold 16 integers each");
+    for (int k = 0; k < 16; k++)
+        TORCH_CHECK(dx[k] >= -16 * CS_MAX_MAP && dx[k] <= 16 * CS_MAX_MAP && dy[k] >= -16 * CS_MAX_MAP && dy[k] <= 16 * CS_MAX_MAP,
+                    "coopsearch: belief_actions: dx and dy must be -1024..1024, got ", dx[k], " and ", dy[k], " at ", k);
+    TORCH_CHECK(state.dim() == 2 && state.size(0) >= 1 && state.size(0) <= INT32_MAX && state.size(1) >= 4 * n_agents &&
+                    state.size(1) <= INT32_MAX,
+                "coopsearch: belief_actions: state must be [B, S] with B >= 1 and S >= 4 n_agents = ", 4 * n_agents);
+    const int64_t B = state.size(0), S = state.size(1);
+    TORCH_CHECK(grid.dim() == 2 && grid.size(0) == B && grid.size(1) == side * side, "coopsearch: belief_actions: grid must be [", B,
+                ", ", side * side, "]");
+    TORCH_CHECK(prev.dim() == 3 && prev.size(0) == B && prev.size(1) == CS_MAX_AGENTS && prev.size(2) == 2,
+                "coopsearch: belief_actions: prev must be [", B, ", ", CS_MAX_AGENTS, ", 2]");
+    TORCH_CHECK(actions.dim() == 2 && actions.size(0) == B && actions.size(1) == n_agents, "coopsearch: belief_actions: actions must be [",
+                B, ", ", n_agents, "]");
+    TORCH_CHECK(state.is_cuda(), "coopsearch: belief_actions: state must be a GPU tensor");
+    check_f32(state, "state", B * S, state);
+    check_dev(grid, "grid", at::kInt, B * side * side, state);
+    check_dev(prev, "prev", at::kInt, B * CS_MAX_AGENTS * 2, state);
+    check_dev(actions, "actions", at::kLong, B * n_agents, state);
+    cs_belief_params p{};
+    p.n_agents = (int32_t)n_agents;
+    p.side = (int32_t)side;
+    p.view_range = (int32_t)view_range;
+    p.keep = (int32_t)keep;
+    p.lookahead = (int32_t)lookahead;
+    p.state_width = (int32_t)S;
+    p.mode = (int32_t)mode;
+    p.moved = (int32_t)moved;
+    p.sense16 = (int32_t)sense16;
+    for (int k = 0; k < 16; k++) {
+        p.dx[k] = (int32_t)dx[k];
+        p.dy[k] = (int32_t)dy[k];
+    }
+    const int rc = cs_belief_actions(&p, state.data_ptr<float>(), (int)B, grid.data_ptr<int32_t>(), prev.data_ptr<int32_t>(),
+                                     actions.data_ptr<int64_t>(), stream_of(state));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
 int64_t abi_version() { return cs_abi_version(); }
 
 // ---- QMIX learner: the GRU recurrence over T steps (cs_gru_seq_forward / cs_gru_seq_backward) ------------------------------
@@ -854,6 +905,8 @@ TORCH_LIBRARY(coopsearch, m) {
           "int layers, int[] colours, Tensor palette, Tensor lut, Tensor(a!) frames) -> ()", &render_episodes);
     m.def("coverage_actions(Tensor state, Tensor(a!) grid, Tensor(b!) actions, int n_agents, int side, int view_range, int keep, "
           "int regrow, int lookahead) -> ()", &coverage_actions);
+    m.def("belief_actions(Tensor state, Tensor(a!) grid, Tensor(b!) prev, Tensor(c!) actions, int n_agents, int side, int view_range, "
+          "int keep, int lookahead, int mode, int moved, int sense16, int[] dx, int[] dy) -> ()", &belief_actions);
     m.def("sweep_episodes(Tensor states, Tensor counts, Tensor(a!) first, Tensor(b!) new_cells, Tensor(c!) seen_cells, int n_agents, "
           "int side, int view_range) -> ()", &sweep_episodes);
     m.def("move_targets(Tensor cfg, Tensor(a!) blob, int mode, int persist, int seed, float speed, float sense, int env_offset) -> ()",

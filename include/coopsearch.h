@@ -40,7 +40,7 @@ extern "C" {
                               cs_episode_returns, then cs_policy_pack_device, then cs_collect_flight, cs_compact_out and
                               cs_store_episodes_compact, then cs_snapshot_bytes, cs_snapshot and cs_restore, then cs_render_params and
                               cs_render_episodes, then cs_gae and cs_ppo_loss, then cs_coverage_params and cs_coverage_actions, then cs_sweep_params and cs_sweep_episodes, then
-                              cs_motion_params and cs_move_targets (no existing export or struct changed: a version-7 caller works unchanged) */
+                              cs_motion_params and cs_move_targets, then cs_belief_params and cs_belief_actions (no existing export or struct changed: a version-7 caller works unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
 #define CS_MAX_MAP 64
@@ -582,6 +582,41 @@ typedef struct cs_motion_params {
  * launch) for a cfg that cs_state_layout refuses, a field out of range, a non-zero `reserved`, a NULL pointer or a state_dev
  * that is not 16-byte aligned.  The message is cs_episodes_last_error()'s (cs_last_error() holds it too). */
 int cs_move_targets(const cs_config *cfg, void *state_dev, const cs_motion_params *p, void *stream);
+
+/* ---- target-density filter policy for moving targets, one launch per decision ----------------
+ * cs_coverage_actions' belief grid knows nothing of motion.  This policy keeps, per env, the expected density D of unfound
+ * targets -- int32 [side * side], row-major [ix * side + iy], Q16: 65536 = one cell's worth of "nobody has looked", the caller
+ * fills it with 65536 when an episode starts; a cell is read as clamp(cell, 0, 2^19), so a whole map sums to at most 2^31 -- and
+ * the quantised positions of the agents at the previous call (prev, read clamped to +-2^15; slots >= n_agents are never
+ * touched).  A call PREDICTS (only if moved): every cell sends its mass through the targets' motion model -- one sixteenth along
+ * each of the 16 headings of cs_move_targets (displacement dx[k], dy[k] sub-units of 1/16 cell), or, in mode CS_MOTION_EVADE for
+ * a cell whose centre lies within sense16 sub-units of an agent's PREVIOUS position, all of it along the heading that leads away
+ * from the nearest such agent -- split bilinearly over four cells, destinations clamped to the map; then it SWEEPS: the cells
+ * within 16 view_range sub-units of a current agent are multiplied by keep / 65536; then the agents CHOOSE as
+ * cs_coverage_actions' do.  DEFINED by belief.belief_actions_torch (stock torch ops, integer after one quantisation); the kernel
+ * reproduces grid, prev and actions element for element.
+ *   state_dev  float [B][state_width] (the first 4 n_agents floats of a get_state() row are read)
+ *   grid_dev   int32 [B][side * side], in / out     prev_dev  int32 [B][8][2], in / out     actions_dev  int64 [B][n_agents], out */
+typedef struct cs_belief_params {
+    int32_t n_agents;     /* 1..8 */
+    int32_t side;         /* map_size: cells per side, 1..CS_MAX_MAP */
+    int32_t view_range;   /* sensor radius in cells, 0..CS_MAX_MAP */
+    int32_t keep;         /* rint((1 - detect_prob) * 65536), 0..65536 */
+    int32_t lookahead;    /* distance of the look-ahead point in cells, 0..side */
+    int32_t state_width;  /* floats per state row, >= 4 n_agents */
+    int32_t mode;         /* the motion model: CS_MOTION_WALK or CS_MOTION_EVADE */
+    int32_t moved;        /* 1: the targets moved since the previous call (predict first); 0: they did not */
+    int32_t sense16;      /* rint(16 sense), 0..2048 (evade only) */
+    int32_t dx[16];       /* rint(16 speed cos(2 pi k / 16)), -1024..1024 */
+    int32_t dy[16];       /* rint(16 speed sin(2 pi k / 16)), -1024..1024 */
+    int32_t reserved;     /* must be 0 (CS_E_CONFIG otherwise) */
+} cs_belief_params;
+
+/* One launch on `stream`, one workgroup per env, atomics on LDS only (integer: the result does not depend on their order), no
+ * synchronisation.  CS_E_CONFIG (before any launch) for a field out of range, a non-zero `reserved`, a NULL or misaligned
+ * pointer or B < 1.  The message is cs_episodes_last_error()'s. */
+int cs_belief_actions(const cs_belief_params *p, const float *state_dev, int B, int32_t *grid_dev, int32_t *prev_dev,
+                      int64_t *actions_dev, void *stream);
 
 /* ---- QMIX learner: the GRU recurrence of the agent network over T steps, forward and backward ---------------------
  * Replaces the per-transition unroll of policy/qmix.py:160-182 (get_q_values) over network/base_net.py:40-46
