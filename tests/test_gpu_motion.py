@@ -99,6 +99,78 @@ def test_moving_env_equals_the_plain_env_moved_by_the_definition(env_name, B, T,
     assert not torch.equal(moving.raw()["tgt"], start)
 
 
+# ---- 2b. ... through every rollout layout, team and reset mode -----------------------------------------------------------------
+
+SWEEP_B, SWEEP_CALLS, SWEEP_LIMIT = 77, (1, 2, 5, 9, 7), 7   # nine full octet wavefronts' worth + a tail of 5; every env ends
+SWEEP_KERNELS = ("group", "oct", "od", "ode", "lane", "lanev")
+SWEEP_TEAMS = [(1, 1, 1), (3, 15, 0), (5, 16, 1), (8, 16, 1)]   # (n_agents, n_targets, target_mode)
+SWEEP_MODES = dict(frozen=dict(freeze_done=True), auto_reset=dict(freeze_done=False, auto_reset=True), unfrozen=dict(freeze_done=False))
+SWEEP_CASES = [(k, n, m, tm, mode, "evade") for k in SWEEP_KERNELS for (n, m, tm) in SWEEP_TEAMS for mode in SWEEP_MODES
+               if not (k == "lanev" and n > 5)]                  # k_rollout_lanev serves teams of up to 5
+SWEEP_CASES += [(k, 5, 16, 1, "auto_reset", "walk") for k in SWEEP_KERNELS]
+
+
+def sweep_args(n, m, tmode):
+    # agent_mode 1, the start line across the middle of the map: within the 7 steps of an episode every team comes within range of
+    # targets (from y = 0 the three agents of the circle layout reach none), so targets are found and evade at the sensing radius
+    args = cs.make_env_args("flight_easy", n_agents=n, agent_mode=1, target_num=m, target_mode=tmode)
+    args.time_limit = SWEEP_LIMIT
+    return args
+
+
+def sweep_motion(args, how):
+    if how == "walk":    # a move before every step: every launch is one step
+        return mo.TargetMotion(mode="walk", speed=0.75, every=1, persist=2, seed=6)
+    return mo.TargetMotion(mode="evade", speed=0.75, every=3, persist=2, sense=float(args.view_range), seed=6)   # hovering at the sensing radius
+
+
+_by_hand = {}
+
+
+def sweep_by_hand(n, m, tmode, mode, how):
+    """The yardstick, once per (team, mode, motion) for the six kernels' cases: a plain kernel="group" env stepped one step at a
+    time, its targets moved by the DEFINITION on the CPU.  -> per call (actions, rows, records after it)."""
+    key = (n, m, tmode, mode, how)
+    if key not in _by_hand:
+        args = sweep_args(n, m, tmode)
+        motion = sweep_motion(args, how)
+        plain = cs.BatchedFlightEnv(args, batch=SWEEP_B, kernel="group", **SWEEP_MODES[mode])
+        g = torch.Generator().manual_seed(100 * n + m)
+        start, calls, phase = plain.raw()["tgt"].clone(), [], 0
+        for T in SWEEP_CALLS:
+            actions = torch.randint(0, 3, (T, SWEEP_B, n), generator=g).to(DEV)
+            rows = drive_by_hand(plain, motion, actions, phase)
+            phase += T
+            calls.append((actions, rows, records(plain).clone()))
+        # reach: some target moved, some target was found, and under auto_reset every env has started a second episode
+        hdr = plain.raw()["hdr"].cpu()
+        assert not torch.equal(plain.raw()["tgt"][:, :m], start[:, :m])
+        assert sum(float((r[0] > 0).sum()) for _a, rows, _r in calls for r in rows) > 0    # a step's reward is positive only by a find
+        if mode == "auto_reset":
+            assert int(hdr[:, _lib.H_EPISODES].min()) >= 2
+        _by_hand[key] = calls
+    return _by_hand[key]
+
+
+@pytest.mark.parametrize("kernel,n,m,tmode,mode,how", SWEEP_CASES,
+                         ids=[f"{k}-n{n}-m{m}-{mode}-{how}" for (k, n, m, _t, mode, how) in SWEEP_CASES])
+def test_moving_env_on_every_rollout_kernel_equals_the_group_env_moved_by_the_definition(kernel, n, m, tmode, mode, how):
+    """Every rollout kernel reloads tgt at launch entry (k_rollout_lanev and k_rollout_od keep the normalised floats in registers
+    from there on), and until now only the pair kernel that "auto" picks had met a target that moved between launches.
+    time_limit 7: every env ends -- and under auto_reset restarts, on the reset's targets -- several times in the 24 steps."""
+    args = sweep_args(n, m, tmode)
+    moving = mo.MovingTargetEnv(args, batch=SWEEP_B, target_motion=sweep_motion(args, how), kernel=kernel, **SWEEP_MODES[mode])
+    phase = 0
+    for actions, rows, recs in sweep_by_hand(n, m, tmode, mode, how):
+        out = moving.rollout(actions)
+        for t, row in enumerate(rows):
+            for name, b in zip(TABLES, row):
+                assert torch.equal(out[name][t], b), (phase + t, name)
+        phase += actions.shape[0]
+        assert moving.motion_phase == phase
+        assert torch.equal(records(moving), recs), phase
+
+
 # ---- 3. one call equals many --------------------------------------------------------------------------------------------------
 
 MOTION3 = mo.TargetMotion(mode="evade", speed=0.5, every=3, persist=2, sense=10.0, seed=11)
