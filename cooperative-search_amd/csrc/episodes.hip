@@ -155,6 +155,7 @@ __global__ __launch_bounds__(256) void k_compact_small(CompactParams p) {
 #include "coverage.h" // k_coverage_actions: the greedy coverage baseline (cs_coverage_actions)
 #include "sweep.h"    // k_sweep_episodes: swept-area accounting of recorded episodes (cs_sweep_episodes)
 #include "belief.h"   // k_belief_actions: the target-density filter policy for moving targets (cs_belief_actions)
+#include "plan.h"     // k_plan_actions: a receding-horizon sequence search over a base policy's grid (cs_plan_actions)
 
 thread_local char g_eerr[160] = "";
 
@@ -350,6 +351,39 @@ int cs_belief_actions(const cs_belief_params *p, const float *state_dev, int B, 
     hipLaunchKernelGGL(k_belief_actions, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
     if (hipGetLastError() != hipSuccess) {
         snprintf(g_eerr, sizeof(g_eerr), "cs_belief_actions: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    return CS_OK;
+}
+
+int cs_plan_actions(const cs_plan_params *p, const float *state_dev, int B, const int32_t *grid_dev, int64_t *actions_dev,
+                    int64_t *plans_dev, int64_t *scores_dev, void *stream) {
+    const char *bad = nullptr;
+    if (!p || !state_dev || !grid_dev || !actions_dev || !plans_dev || !scores_dev) bad = "a NULL pointer";
+    else if (B < 1) bad = "B must be >= 1";
+    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
+    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
+    else if (p->view_range < 0 || p->view_range > CS_MAX_MAP) bad = "view_range must be 0..64";
+    else if (p->depth < 1 || p->depth > PLAN_MAX_DEPTH) bad = "depth must be 1..5";
+    else if (p->stride < 1 || p->stride > PLAN_MAX_STRIDE) bad = "stride must be 1..8";
+    else if (p->discount < 0 || p->discount > 256) bad = "discount must be 0..256";
+    else if (p->state_width < 4 * p->n_agents) bad = "state_width must be at least 4 n_agents";
+    else if (p->reserved != 0) bad = "reserved must be 0";
+    else if ((uintptr_t)grid_dev % 4 != 0 || (uintptr_t)state_dev % 4 != 0 || (uintptr_t)actions_dev % 8 != 0 ||
+             (uintptr_t)plans_dev % 8 != 0 || (uintptr_t)scores_dev % 8 != 0)
+        bad = "a pointer is not aligned to its element size";
+    if (bad) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_plan_actions: %s", bad);
+        return CS_E_CONFIG;
+    }
+    const int cells = p->side * p->side;
+    int seqs = 1;
+    for (int d = 0; d < p->depth; d++) seqs *= 3;
+    const PlanArgs a{state_dev, grid_dev, actions_dev, plans_dev, scores_dev, p->n_agents, p->side, p->state_width, 16 * p->view_range,
+                     p->depth, p->stride, p->discount, (3 * seqs - 3) / 2, seqs, (cells % 4 == 0 && (uintptr_t)grid_dev % 16 == 0) ? 1 : 0};
+    hipLaunchKernelGGL(k_plan_actions, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_plan_actions: kernel launch failed");
         return CS_E_LAUNCH;
     }
     return CS_OK;

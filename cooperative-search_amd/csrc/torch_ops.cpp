@@ -742,6 +742,42 @@ void belief_actions(const Tensor &state, Tensor grid, Tensor prev, Tensor action
     TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
 }
 
+// ---- receding-horizon planner (cs_plan_actions): state [B, S >= 4n] float32, grid [B, side * side] int32 (in), actions, plans and
+// scores [B, n] int64 (out).  Integers and shapes first (nothing is dereferenced), then the tensors.
+void plan_actions(const Tensor &state, const Tensor &grid, Tensor actions, Tensor plans, Tensor scores, int64_t n_agents, int64_t side,
+                  int64_t view_range, int64_t depth, int64_t stride, int64_t discount) {
+    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: plan_actions: n_agents must be 1..8, got ", n_agents);
+    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: plan_actions: side must be 1..", CS_MAX_MAP, ", got ", side);
+    TORCH_CHECK(view_range >= 0 && view_range <= CS_MAX_MAP, "coopsearch: plan_actions: view_range must be 0..", CS_MAX_MAP, ", got ",
+                view_range);
+    TORCH_CHECK(depth >= 1 && depth <= 5, "coopsearch: plan_actions: depth must be 1..5, got ", depth);
+    TORCH_CHECK(stride >= 1 && stride <= 8, "coopsearch: plan_actions: stride must be 1..8, got ", stride);
+    TORCH_CHECK(discount >= 0 && discount <= 256, "coopsearch: plan_actions: discount must be 0..256, got ", discount);
+    TORCH_CHECK(state.dim() == 2 && state.size(0) >= 1 && state.size(0) <= INT32_MAX && state.size(1) >= 4 * n_agents &&
+                    state.size(1) <= INT32_MAX,
+                "coopsearch: plan_actions: state must be [B, S] with B >= 1 and S >= 4 n_agents = ", 4 * n_agents);
+    const int64_t B = state.size(0), S = state.size(1);
+    TORCH_CHECK(grid.dim() == 2 && grid.size(0) == B && grid.size(1) == side * side, "coopsearch: plan_actions: grid must be [", B, ", ",
+                side * side, "]");
+    TORCH_CHECK(actions.dim() == 2 && actions.size(0) == B && actions.size(1) == n_agents, "coopsearch: plan_actions: actions must be [",
+                B, ", ", n_agents, "]");
+    TORCH_CHECK(plans.dim() == 2 && plans.size(0) == B && plans.size(1) == n_agents, "coopsearch: plan_actions: plans must be [", B, ", ",
+                n_agents, "]");
+    TORCH_CHECK(scores.dim() == 2 && scores.size(0) == B && scores.size(1) == n_agents, "coopsearch: plan_actions: scores must be [", B,
+                ", ", n_agents, "]");
+    TORCH_CHECK(state.is_cuda(), "coopsearch: plan_actions: state must be a GPU tensor");
+    check_f32(state, "state", B * S, state);
+    check_dev(grid, "grid", at::kInt, B * side * side, state);
+    check_dev(actions, "actions", at::kLong, B * n_agents, state);
+    check_dev(plans, "plans", at::kLong, B * n_agents, state);
+    check_dev(scores, "scores", at::kLong, B * n_agents, state);
+    const cs_plan_params p{(int32_t)n_agents, (int32_t)side, (int32_t)view_range, (int32_t)depth, (int32_t)stride, (int32_t)discount,
+                           (int32_t)S, 0};
+    const int rc = cs_plan_actions(&p, state.data_ptr<float>(), (int)B, grid.data_ptr<int32_t>(), actions.data_ptr<int64_t>(),
+                                   plans.data_ptr<int64_t>(), scores.data_ptr<int64_t>(), stream_of(state));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
 int64_t abi_version() { return cs_abi_version(); }
 
 // ---- QMIX learner: the GRU recurrence over T steps (cs_gru_seq_forward / cs_gru_seq_backward) ------------------------------
@@ -907,6 +943,8 @@ TORCH_LIBRARY(coopsearch, m) {
           "int regrow, int lookahead) -> ()", &coverage_actions);
     m.def("belief_actions(Tensor state, Tensor(a!) grid, Tensor(b!) prev, Tensor(c!) actions, int n_agents, int side, int view_range, "
           "int keep, int lookahead, int mode, int moved, int sense16, int[] dx, int[] dy) -> ()", &belief_actions);
+    m.def("plan_actions(Tensor state, Tensor grid, Tensor(a!) actions, Tensor(b!) plans, Tensor(c!) scores, int n_agents, int side, "
+          "int view_range, int depth, int stride, int discount) -> ()", &plan_actions);
     m.def("sweep_episodes(Tensor states, Tensor counts, Tensor(a!) first, Tensor(b!) new_cells, Tensor(c!) seen_cells, int n_agents, "
           "int side, int view_range) -> ()", &sweep_episodes);
     m.def("move_targets(Tensor cfg, Tensor(a!) blob, int mode, int persist, int seed, float speed, float sense, int env_offset) -> ()",

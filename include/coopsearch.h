@@ -40,7 +40,8 @@ extern "C" {
                               cs_episode_returns, then cs_policy_pack_device, then cs_collect_flight, cs_compact_out and
                               cs_store_episodes_compact, then cs_snapshot_bytes, cs_snapshot and cs_restore, then cs_render_params and
                               cs_render_episodes, then cs_gae and cs_ppo_loss, then cs_coverage_params and cs_coverage_actions, then cs_sweep_params and cs_sweep_episodes, then
-                              cs_motion_params and cs_move_targets, then cs_belief_params and cs_belief_actions (no existing export or struct changed: a version-7 caller works unchanged) */
+                              cs_motion_params and cs_move_targets, then cs_belief_params and cs_belief_actions,
+                              then cs_plan_params and cs_plan_actions (no existing export or struct changed: a version-7 caller works unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
 #define CS_MAX_MAP 64
@@ -617,6 +618,36 @@ typedef struct cs_belief_params {
  * pointer or B < 1.  The message is cs_episodes_last_error()'s. */
 int cs_belief_actions(const cs_belief_params *p, const float *state_dev, int B, int32_t *grid_dev, int32_t *prev_dev,
                       int64_t *actions_dev, void *stream);
+
+/* ---- receding-horizon planner over a base policy's grid, one launch per decision -------------
+ * cs_coverage_actions and cs_belief_actions score three look-ahead points whose footprints overlap almost entirely: mass abeam of
+ * an agent or behind it scores 0 on all three and the agent flies straight on.  This planner reads the grid either of them left
+ * (int32 [side * side], row-major [ix * side + iy]; READ ONLY, every cell as clamp(cell, 0, 2^19), so a whole map sums to at most
+ * 2^31) and, per env, lets the agents decide in index order on a working copy W: the 3^depth sequences of `depth` segments, each
+ * "hold action a for `stride` steps" (one step: h = (h + {0, 1, 35}[a]) % 36, x = clamp(x + ((16 CT[h]) >> 14), 0, 16 side), y
+ * likewise), are scored by the sum over their segment end points of (the mass of W within 16 view_range sub-units of the point and
+ * of no earlier point of the sequence) * w_d, w_0 = 256, w_d = (w_{d-1} discount) >> 8; the lowest sequence index of the largest
+ * score wins (the index: `depth` base-3 digits, the first segment the most significant), the action is its first digit, and W is
+ * zeroed on that sequence's discs before the next agent decides.  DEFINED by plan.plan_actions_torch (stock torch ops, integer
+ * after one quantisation); the kernel reproduces actions, plans and scores element for element.
+ *   state_dev  float [B][state_width] (the first 4 n_agents floats of a get_state() row are read)
+ *   grid_dev   int32 [B][side * side], in     actions_dev, plans_dev, scores_dev  int64 [B][n_agents], out: the action, the
+ *   winning sequence index and its score (at most 2^39) */
+typedef struct cs_plan_params {
+    int32_t n_agents;     /* 1..8 */
+    int32_t side;         /* map_size: cells per side, 1..CS_MAX_MAP */
+    int32_t view_range;   /* sensor radius in cells, 0..CS_MAX_MAP */
+    int32_t depth;        /* segments per sequence, 1..5 */
+    int32_t stride;       /* env steps per segment, 1..8 */
+    int32_t discount;     /* Q8 weight ratio of successive segments, 0..256 */
+    int32_t state_width;  /* floats per state row, >= 4 n_agents */
+    int32_t reserved;     /* must be 0 (CS_E_CONFIG otherwise) */
+} cs_plan_params;
+
+/* One launch on `stream`, one workgroup per env, no atomics, no synchronisation.  CS_E_CONFIG (before any launch) for a field out
+ * of range, a non-zero `reserved`, a NULL or misaligned pointer or B < 1.  The message is cs_episodes_last_error()'s. */
+int cs_plan_actions(const cs_plan_params *p, const float *state_dev, int B, const int32_t *grid_dev, int64_t *actions_dev,
+                    int64_t *plans_dev, int64_t *scores_dev, void *stream);
 
 /* ---- QMIX learner: the GRU recurrence of the agent network over T steps, forward and backward ---------------------
  * Replaces the per-transition unroll of policy/qmix.py:160-182 (get_q_values) over network/base_net.py:40-46
