@@ -24,6 +24,7 @@ from .sweep import sweep_bonus, with_sweep_bonus, collect_sweep_data  # noqa: F4
 from .motion import TargetMotion, MovingTargetEnv, move_targets_torch, make_env  # noqa: F401
 from .belief import BeliefAgents, BeliefModel, belief_actions_torch  # noqa: F401
 from .plan import PlanAgents, plan_actions_torch  # noqa: F401
+from .forecast import ForecastAgents, forecast_torch, plan_forecast_actions_torch  # noqa: F401
 from .render import RenderSpec, episode_tables, render_episodes, render_episodes_torch, write_frames  # noqa: F401
 
 __all__ = ["BatchedFlightEnv", "FlightSearchEnvEasy", "FlightSearchEnv", "load_targets", "default_circle_dict",

@@ -156,6 +156,7 @@ __global__ __launch_bounds__(256) void k_compact_small(CompactParams p) {
 #include "sweep.h"    // k_sweep_episodes: swept-area accounting of recorded episodes (cs_sweep_episodes)
 #include "belief.h"   // k_belief_actions: the target-density filter policy for moving targets (cs_belief_actions)
 #include "plan.h"     // k_plan_actions: a receding-horizon sequence search over a base policy's grid (cs_plan_actions)
+#include "forecast.h" // k_belief_forecast, k_plan_forecast_actions: the density along the horizon and the search scored on it
 
 thread_local char g_eerr[160] = "";
 
@@ -384,6 +385,95 @@ int cs_plan_actions(const cs_plan_params *p, const float *state_dev, int B, cons
     hipLaunchKernelGGL(k_plan_actions, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
     if (hipGetLastError() != hipSuccess) {
         snprintf(g_eerr, sizeof(g_eerr), "cs_plan_actions: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    return CS_OK;
+}
+
+int cs_belief_forecast(const cs_forecast_params *p, const int32_t *grid_dev, const int32_t *pos_dev, int B, int32_t *stack_dev,
+                       void *stream) {
+    const char *bad = nullptr;
+    if (!p || !grid_dev || !pos_dev || !stack_dev) bad = "a NULL pointer";
+    else if (B < 1) bad = "B must be >= 1";
+    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
+    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
+    else if (p->levels < 1 || p->levels > FC_MAX_LEVELS) bad = "levels must be 1..5";
+    else if (p->mode != CS_MOTION_WALK && p->mode != CS_MOTION_EVADE) bad = "mode must be CS_MOTION_WALK or CS_MOTION_EVADE";
+    else if (p->sense16 < 0 || p->sense16 > 32 * CS_MAX_MAP) bad = "sense16 must be 0..2048";
+    else if (p->reserved != 0) bad = "reserved must be 0";
+    else if ((uintptr_t)grid_dev % 4 != 0 || (uintptr_t)pos_dev % 4 != 0 || (uintptr_t)stack_dev % 4 != 0)
+        bad = "a pointer is not aligned to its element size";
+    for (int k = 0; !bad && k < 16; k++)
+        if (p->dx[k] < -16 * CS_MAX_MAP || p->dx[k] > 16 * CS_MAX_MAP || p->dy[k] < -16 * CS_MAX_MAP || p->dy[k] > 16 * CS_MAX_MAP)
+            bad = "dx and dy must be -1024..1024";
+    for (int d = 0; !bad && d < FC_MAX_LEVELS; d++)
+        if (p->moves[d] < 0 || p->moves[d] > PLAN_MAX_STRIDE || (d >= p->levels && p->moves[d] != 0))
+            bad = "moves must be 0..8, and 0 beyond `levels`";
+    if (bad) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_belief_forecast: %s", bad);
+        return CS_E_CONFIG;
+    }
+    const int cells = p->side * p->side;
+    ForecastArgs a{};
+    a.b.c.n = p->n_agents;
+    a.b.c.side = p->side;
+    a.b.mode = p->mode;
+    a.b.sense2 = (unsigned)p->sense16 * (unsigned)p->sense16;
+    for (int k = 0; k < 16; k++) {
+        a.b.dx[k] = p->dx[k];
+        a.b.dy[k] = p->dy[k];
+    }
+    a.grid = grid_dev;
+    a.pos = pos_dev;
+    a.stack = stack_dev;
+    a.levels = p->levels;
+    for (int d = 0; d < FC_MAX_LEVELS; d++) a.moves[d] = p->moves[d];
+    a.vec_in = (cells % 4 == 0 && (uintptr_t)grid_dev % 16 == 0) ? 1 : 0;
+    a.vec_out = (cells % 4 == 0 && (uintptr_t)stack_dev % 16 == 0) ? 1 : 0;
+    hipLaunchKernelGGL(k_belief_forecast, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_belief_forecast: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    return CS_OK;
+}
+
+int cs_plan_forecast_actions(const cs_plan_params *p, const float *state_dev, int B, const int32_t *stack_dev, int64_t *actions_dev,
+                             int64_t *plans_dev, int64_t *scores_dev, void *stream) {
+    const char *bad = nullptr;
+    if (!p || !state_dev || !stack_dev || !actions_dev || !plans_dev || !scores_dev) bad = "a NULL pointer";
+    else if (B < 1) bad = "B must be >= 1";
+    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
+    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
+    else if (p->view_range < 0 || p->view_range > CS_MAX_MAP) bad = "view_range must be 0..64";
+    else if (p->depth < 1 || p->depth > PLAN_MAX_DEPTH) bad = "depth must be 1..5";
+    else if (p->stride < 1 || p->stride > PLAN_MAX_STRIDE) bad = "stride must be 1..8";
+    else if (p->discount < 0 || p->discount > 256) bad = "discount must be 0..256";
+    else if (p->state_width < 4 * p->n_agents) bad = "state_width must be at least 4 n_agents";
+    else if (p->reserved != 0) bad = "reserved must be 0";
+    else if ((uintptr_t)stack_dev % 4 != 0 || (uintptr_t)state_dev % 4 != 0 || (uintptr_t)actions_dev % 8 != 0 ||
+             (uintptr_t)plans_dev % 8 != 0 || (uintptr_t)scores_dev % 8 != 0)
+        bad = "a pointer is not aligned to its element size";
+    if (bad) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_plan_forecast_actions: %s", bad);
+        return CS_E_CONFIG;
+    }
+    const int cells = p->side * p->side, level_words = (cells + 3) & ~3;
+    int seqs = 1;
+    for (int d = 0; d < p->depth; d++) seqs *= 3;
+    const PlanArgs a{state_dev, stack_dev, actions_dev, plans_dev, scores_dev, p->n_agents, p->side, p->state_width, 16 * p->view_range,
+                     p->depth, p->stride, p->discount, (3 * seqs - 3) / 2, seqs, (cells % 4 == 0 && (uintptr_t)stack_dev % 16 == 0) ? 1 : 0};
+    const size_t lds = fc_plan_lds_bytes(p->depth, level_words);
+    // more than 64 KB of dynamic LDS (side 64 with depth 4 or 5) is granted only to a kernel that asked for it
+    if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void *>(&k_plan_forecast_actions),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        (void)hipGetLastError();
+        snprintf(g_eerr, sizeof(g_eerr), "cs_plan_forecast_actions: the device does not grant %zu bytes of LDS", lds);
+        return CS_E_LAUNCH;
+    }
+    hipLaunchKernelGGL(k_plan_forecast_actions, dim3((unsigned)B), dim3(COV_THREADS), lds, (hipStream_t)stream, a, level_words);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_plan_forecast_actions: kernel launch failed");
         return CS_E_LAUNCH;
     }
     return CS_OK;

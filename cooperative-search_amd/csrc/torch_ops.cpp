@@ -778,6 +778,84 @@ void plan_actions(const Tensor &state, const Tensor &grid, Tensor actions, Tenso
     TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
 }
 
+// ---- the density along the planning horizon (cs_belief_forecast): grid [B, side * side] int32 (in), pos [B, 8, 2] int32 (in),
+// stack [B, L, side * side] int32 (out), L = moves.size().  Integers and shapes first (nothing is dereferenced), then the tensors.
+void belief_forecast(const Tensor &grid, const Tensor &pos, Tensor stack, int64_t n_agents, int64_t side, int64_t mode, int64_t sense16,
+                     at::IntArrayRef dx, at::IntArrayRef dy, at::IntArrayRef moves) {
+    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: belief_forecast: n_agents must be 1..8, got ", n_agents);
+    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: belief_forecast: side must be 1..", CS_MAX_MAP, ", got ", side);
+    TORCH_CHECK(mode == CS_MOTION_WALK || mode == CS_MOTION_EVADE, "coopsearch: belief_forecast: mode must be 0 (walk) or 1 (evade), got ", mode);
+    TORCH_CHECK(sense16 >= 0 && sense16 <= 32 * CS_MAX_MAP, "coopsearch: belief_forecast: sense16 must be 0..", 32 * CS_MAX_MAP, ", got ", sense16);
+    TORCH_CHECK(dx.size() == 16 && dy.size() == 16, "coopsearch: belief_forecast: dx and dy must hold 16 integers each");
+    for (int k = 0; k < 16; k++)
+        TORCH_CHECK(dx[k] >= -16 * CS_MAX_MAP && dx[k] <= 16 * CS_MAX_MAP && dy[k] >= -16 * CS_MAX_MAP && dy[k] <= 16 * CS_MAX_MAP,
+                    "coopsearch: belief_forecast: dx and dy must be -1024..1024, got ", dx[k], " and ", dy[k], " at ", k);
+    TORCH_CHECK(moves.size() >= 1 && moves.size() <= 5, "coopsearch: belief_forecast: moves must hold 1..5 integers, got ", moves.size());
+    const int64_t L = (int64_t)moves.size();
+    for (int64_t d = 0; d < L; d++)
+        TORCH_CHECK(moves[d] >= 0 && moves[d] <= 8, "coopsearch: belief_forecast: moves must be 0..8, got ", moves[d], " at ", d);
+    TORCH_CHECK(grid.dim() == 2 && grid.size(0) >= 1 && grid.size(0) <= INT32_MAX && grid.size(1) == side * side,
+                "coopsearch: belief_forecast: grid must be [B, ", side * side, "] with B >= 1");
+    const int64_t B = grid.size(0);
+    TORCH_CHECK(pos.dim() == 3 && pos.size(0) == B && pos.size(1) == CS_MAX_AGENTS && pos.size(2) == 2,
+                "coopsearch: belief_forecast: pos must be [", B, ", ", CS_MAX_AGENTS, ", 2]");
+    TORCH_CHECK(stack.dim() == 3 && stack.size(0) == B && stack.size(1) == L && stack.size(2) == side * side,
+                "coopsearch: belief_forecast: stack must be [", B, ", ", L, ", ", side * side, "]");
+    TORCH_CHECK(grid.is_cuda(), "coopsearch: belief_forecast: grid must be a GPU tensor");
+    check_dev(grid, "grid", at::kInt, B * side * side, grid);
+    check_dev(pos, "pos", at::kInt, B * CS_MAX_AGENTS * 2, grid);
+    check_dev(stack, "stack", at::kInt, B * L * side * side, grid);
+    cs_forecast_params p{};
+    p.n_agents = (int32_t)n_agents;
+    p.side = (int32_t)side;
+    p.levels = (int32_t)L;
+    p.mode = (int32_t)mode;
+    p.sense16 = (int32_t)sense16;
+    for (int k = 0; k < 16; k++) {
+        p.dx[k] = (int32_t)dx[k];
+        p.dy[k] = (int32_t)dy[k];
+    }
+    for (int64_t d = 0; d < L; d++) p.moves[d] = (int32_t)moves[d];
+    const int rc = cs_belief_forecast(&p, grid.data_ptr<int32_t>(), pos.data_ptr<int32_t>(), (int)B, stack.data_ptr<int32_t>(), stream_of(grid));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
+// ---- the planner scored on the forecast (cs_plan_forecast_actions): plan_actions with stack [B, depth, side * side] int32 (in) in
+// the grid's place.  Integers and shapes first (nothing is dereferenced), then the tensors.
+void plan_forecast_actions(const Tensor &state, const Tensor &stack, Tensor actions, Tensor plans, Tensor scores, int64_t n_agents,
+                           int64_t side, int64_t view_range, int64_t depth, int64_t stride, int64_t discount) {
+    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: plan_forecast_actions: n_agents must be 1..8, got ", n_agents);
+    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: plan_forecast_actions: side must be 1..", CS_MAX_MAP, ", got ", side);
+    TORCH_CHECK(view_range >= 0 && view_range <= CS_MAX_MAP, "coopsearch: plan_forecast_actions: view_range must be 0..", CS_MAX_MAP,
+                ", got ", view_range);
+    TORCH_CHECK(depth >= 1 && depth <= 5, "coopsearch: plan_forecast_actions: depth must be 1..5, got ", depth);
+    TORCH_CHECK(stride >= 1 && stride <= 8, "coopsearch: plan_forecast_actions: stride must be 1..8, got ", stride);
+    TORCH_CHECK(discount >= 0 && discount <= 256, "coopsearch: plan_forecast_actions: discount must be 0..256, got ", discount);
+    TORCH_CHECK(state.dim() == 2 && state.size(0) >= 1 && state.size(0) <= INT32_MAX && state.size(1) >= 4 * n_agents &&
+                    state.size(1) <= INT32_MAX,
+                "coopsearch: plan_forecast_actions: state must be [B, S] with B >= 1 and S >= 4 n_agents = ", 4 * n_agents);
+    const int64_t B = state.size(0), S = state.size(1);
+    TORCH_CHECK(stack.dim() == 3 && stack.size(0) == B && stack.size(1) == depth && stack.size(2) == side * side,
+                "coopsearch: plan_forecast_actions: stack must be [", B, ", ", depth, ", ", side * side, "]");
+    TORCH_CHECK(actions.dim() == 2 && actions.size(0) == B && actions.size(1) == n_agents,
+                "coopsearch: plan_forecast_actions: actions must be [", B, ", ", n_agents, "]");
+    TORCH_CHECK(plans.dim() == 2 && plans.size(0) == B && plans.size(1) == n_agents, "coopsearch: plan_forecast_actions: plans must be [", B,
+                ", ", n_agents, "]");
+    TORCH_CHECK(scores.dim() == 2 && scores.size(0) == B && scores.size(1) == n_agents, "coopsearch: plan_forecast_actions: scores must be [",
+                B, ", ", n_agents, "]");
+    TORCH_CHECK(state.is_cuda(), "coopsearch: plan_forecast_actions: state must be a GPU tensor");
+    check_f32(state, "state", B * S, state);
+    check_dev(stack, "stack", at::kInt, B * depth * side * side, state);
+    check_dev(actions, "actions", at::kLong, B * n_agents, state);
+    check_dev(plans, "plans", at::kLong, B * n_agents, state);
+    check_dev(scores, "scores", at::kLong, B * n_agents, state);
+    const cs_plan_params p{(int32_t)n_agents, (int32_t)side, (int32_t)view_range, (int32_t)depth, (int32_t)stride, (int32_t)discount,
+                           (int32_t)S, 0};
+    const int rc = cs_plan_forecast_actions(&p, state.data_ptr<float>(), (int)B, stack.data_ptr<int32_t>(), actions.data_ptr<int64_t>(),
+                                            plans.data_ptr<int64_t>(), scores.data_ptr<int64_t>(), stream_of(state));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
 int64_t abi_version() { return cs_abi_version(); }
 
 // ---- QMIX learner: the GRU recurrence over T steps (cs_gru_seq_forward / cs_gru_seq_backward) ------------------------------
@@ -945,6 +1023,10 @@ TORCH_LIBRARY(coopsearch, m) {
           "int keep, int lookahead, int mode, int moved, int sense16, int[] dx, int[] dy) -> ()", &belief_actions);
     m.def("plan_actions(Tensor state, Tensor grid, Tensor(a!) actions, Tensor(b!) plans, Tensor(c!) scores, int n_agents, int side, "
           "int view_range, int depth, int stride, int discount) -> ()", &plan_actions);
+    m.def("belief_forecast(Tensor grid, Tensor pos, Tensor(a!) stack, int n_agents, int side, int mode, int sense16, int[] dx, int[] dy, "
+          "int[] moves) -> ()", &belief_forecast);
+    m.def("plan_forecast_actions(Tensor state, Tensor stack, Tensor(a!) actions, Tensor(b!) plans, Tensor(c!) scores, int n_agents, "
+          "int side, int view_range, int depth, int stride, int discount) -> ()", &plan_forecast_actions);
     m.def("sweep_episodes(Tensor states, Tensor counts, Tensor(a!) first, Tensor(b!) new_cells, Tensor(c!) seen_cells, int n_agents, "
           "int side, int view_range) -> ()", &sweep_episodes);
     m.def("move_targets(Tensor cfg, Tensor(a!) blob, int mode, int persist, int seed, float speed, float sense, int env_offset) -> ()",

@@ -72,8 +72,9 @@ def _check_tensors(state, grid, n, side):
         raise ValueError(f"plan: grid must be int32 [{state.shape[0]}, {side * side}] on the state's device")
 
 
-def _plan_rows(state, grid, n, side, view_range, depth, stride, discount):
-    """The definition on a block of envs: (actions, plans, scores), int64 [B, n]."""
+def _plan_rows(state, levels, n, side, view_range, depth, stride, discount):
+    """The definition on a block of envs: (actions, plans, scores), int64 [B, n].  levels: int32 [B, L, side * side]; L = 1: the
+    grid, every segment is scored on it; L = depth: segment d is scored on level d (forecast.plan_forecast_actions_torch)."""
     i64, dev = torch.int64, state.device
     B, R2, lim, cells = int(state.shape[0]), (16 * view_range) ** 2, 16 * side, side * side
     X, Y, h = bl.quantise(state, n, side)
@@ -86,7 +87,8 @@ def _plan_rows(state, grid, n, side, view_range, depth, stride, discount):
         dx, dy = centre - px.unsqueeze(-1), centre - py.unsqueeze(-1)
         return ((dx * dx).unsqueeze(-1) + (dy * dy).unsqueeze(-2) <= R2).reshape(B, -1, cells)
 
-    W = grid.to(i64).clamp(0, CAP)
+    W = levels.to(i64).clamp(0, CAP)
+    last = W.shape[1] - 1
     zero = torch.zeros((), dtype=i64, device=dev)
     actions = torch.empty(B, n, dtype=i64, device=dev)
     plans, scores = torch.empty_like(actions), torch.empty_like(actions)
@@ -103,7 +105,7 @@ def _plan_rows(state, grid, n, side, view_range, depth, stride, discount):
                 y = torch.clamp(y + sy[hh], 0, lim)
             covered = covered.repeat_interleave(3, dim=1)
             disc = within(x, y)
-            gain = torch.where(disc & ~covered, W.unsqueeze(1), zero).sum(-1)      # [B, 3^(d + 1)]
+            gain = torch.where(disc & ~covered, W[:, min(d, last)].unsqueeze(1), zero).sum(-1)     # [B, 3^(d + 1)]
             score = score.repeat_interleave(3, dim=1) + gain * w[d]
             covered = covered | disc
         top = score.max(dim=1, keepdim=True).values
@@ -113,7 +115,7 @@ def _plan_rows(state, grid, n, side, view_range, depth, stride, discount):
         scores[:, i] = top[:, 0]
         actions[:, i] = best // (3 ** (depth - 1))
         chosen = covered.gather(1, best.view(B, 1, 1).expand(B, 1, cells))[:, 0]
-        W = torch.where(chosen, zero, W)
+        W = torch.where(chosen.unsqueeze(1), zero, W)   # in every level
     return actions, plans, scores
 
 
@@ -126,7 +128,7 @@ def plan_actions_torch(state, grid, n_agents, side, view_range, depth, stride, d
     _check_params(n, side, view_range, depth, stride, discount)
     _check_tensors(state, grid, n, side)
     rows = max(1, _CHUNK // (3 ** depth * side * side))   # envs are independent: a large batch goes block by block
-    parts = [_plan_rows(state[b:b + rows], grid[b:b + rows], n, side, view_range, depth, stride, discount)
+    parts = [_plan_rows(state[b:b + rows], grid[b:b + rows].unsqueeze(1), n, side, view_range, depth, stride, discount)
              for b in range(0, int(state.shape[0]), rows)]
     actions, plans, scores = (torch.cat(t) for t in zip(*parts))
     return (actions, plans, scores) if return_plans else actions

@@ -41,7 +41,8 @@ extern "C" {
                               cs_store_episodes_compact, then cs_snapshot_bytes, cs_snapshot and cs_restore, then cs_render_params and
                               cs_render_episodes, then cs_gae and cs_ppo_loss, then cs_coverage_params and cs_coverage_actions, then cs_sweep_params and cs_sweep_episodes, then
                               cs_motion_params and cs_move_targets, then cs_belief_params and cs_belief_actions,
-                              then cs_plan_params and cs_plan_actions (no existing export or struct changed: a version-7 caller works unchanged) */
+                              then cs_plan_params and cs_plan_actions, then cs_forecast_params, cs_belief_forecast and cs_plan_forecast_actions
+                              (no existing export or struct changed: a version-7 caller works unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
 #define CS_MAX_MAP 64
@@ -648,6 +649,38 @@ typedef struct cs_plan_params {
  * of range, a non-zero `reserved`, a NULL or misaligned pointer or B < 1.  The message is cs_episodes_last_error()'s. */
 int cs_plan_actions(const cs_plan_params *p, const float *state_dev, int B, const int32_t *grid_dev, int64_t *actions_dev,
                     int64_t *plans_dev, int64_t *scores_dev, void *stream);
+
+/* ---- the density predicted along the planning horizon, and the planner scored on it ----------
+ * cs_plan_actions scores every segment of a sequence on the density of NOW; moving targets leave it within a few steps.
+ * cs_belief_forecast runs cs_belief_actions' prediction step forward with the agents held at pos: level d of `stack` is the
+ * grid (every cell read as clamp(cell, 0, 2^19)) after moves[0] + .. + moves[d] prediction steps, each capped at 2^19; a level
+ * with moves[d] == 0 is a copy of the level before it (of the clamped grid for d = 0).  cs_plan_forecast_actions is
+ * cs_plan_actions with `depth` levels: the gain of a segment end point d is summed over level d, and the winner's discs are
+ * zeroed in every level.  DEFINED by forecast.forecast_torch and forecast.plan_forecast_actions_torch (stock torch ops, all
+ * integer); the kernels reproduce them element for element.  A stack of identical levels gives cs_plan_actions' outputs.
+ *   grid_dev   int32 [B][side * side], in     pos_dev  int32 [B][8][2], in (cs_belief_actions' prev, read clamped to +-2^15)
+ *   stack_dev  int32 [B][levels][side * side], out of cs_belief_forecast, in (READ ONLY) of cs_plan_forecast_actions, whose
+ *   `depth` is the number of levels; state_dev, actions_dev, plans_dev, scores_dev as cs_plan_actions' */
+typedef struct cs_forecast_params {
+    int32_t n_agents;     /* 1..8 */
+    int32_t side;         /* map_size: cells per side, 1..CS_MAX_MAP */
+    int32_t levels;       /* levels of the stack, 1..5 */
+    int32_t mode;         /* the motion model: CS_MOTION_WALK or CS_MOTION_EVADE */
+    int32_t sense16;      /* rint(16 sense), 0..2048 (evade only) */
+    int32_t dx[16];       /* rint(16 speed cos(2 pi k / 16)), -1024..1024 */
+    int32_t dy[16];       /* rint(16 speed sin(2 pi k / 16)), -1024..1024 */
+    int32_t moves[5];     /* prediction steps from level d - 1 to level d, 0..8; 0 for d >= levels */
+    int32_t reserved;     /* must be 0 (CS_E_CONFIG otherwise) */
+} cs_forecast_params;
+
+/* One launch each on `stream`, one workgroup per env, atomics on LDS only (cs_belief_forecast; integer: the result does not
+ * depend on their order), no synchronisation.  cs_plan_forecast_actions takes 3.3 KB + 4 depth side^2 bytes of LDS (85 KB at
+ * side 64 and depth 5).  CS_E_CONFIG (before any launch) for a field out of range, a non-zero `reserved`, a NULL or misaligned
+ * pointer or B < 1.  The message is cs_episodes_last_error()'s. */
+int cs_belief_forecast(const cs_forecast_params *p, const int32_t *grid_dev, const int32_t *pos_dev, int B, int32_t *stack_dev,
+                       void *stream);
+int cs_plan_forecast_actions(const cs_plan_params *p, const float *state_dev, int B, const int32_t *stack_dev, int64_t *actions_dev,
+                             int64_t *plans_dev, int64_t *scores_dev, void *stream);
 
 /* ---- QMIX learner: the GRU recurrence of the agent network over T steps, forward and backward ---------------------
  * Replaces the per-transition unroll of policy/qmix.py:160-182 (get_q_values) over network/base_net.py:40-46
