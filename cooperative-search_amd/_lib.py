@@ -21,8 +21,8 @@ FREEZE_DONE, AUTO_RESET, ACTIONS_I64, KERNEL_GROUP, KERNEL_LANE, KERNEL_SOLO, KE
 
 EXPORTS = ["cs_abi_version", "cs_source_hash", "cs_has_legacy_kernels", "cs_last_error", "cs_state_layout", "cs_init", "cs_seed", "cs_reset", "cs_step",
            "cs_rollout", "cs_rollout_policy", "cs_rollout_policy_flight", "cs_collect_flight", "cs_emit", "cs_snapshot_bytes", "cs_snapshot", "cs_restore", "cs_metrics", "cs_mt_canonical", "cs_mt_advance", "cs_policy_packed_floats", "cs_policy_pack", "cs_policy_pack_device", "cs_policy_forward",
-           "cs_policy_conv_features", "cs_policy_conv_features_backward_scratch", "cs_policy_conv_features_backward", "cs_policy_last_error", "cs_store_episodes", "cs_store_episodes_compact", "cs_render_episodes", "cs_coverage_actions", "cs_sweep_episodes", "cs_move_targets", "cs_belief_actions", "cs_plan_actions", "cs_belief_forecast", "cs_plan_forecast_actions", "cs_episodes_last_error", "cs_epsilon_step",
-           "cs_gru_seq_forward", "cs_gru_seq_backward", "cs_episode_returns", "cs_gae", "cs_ppo_loss", "cs_learn_last_error"]
+           "cs_policy_conv_features", "cs_policy_conv_features_backward_scratch", "cs_policy_conv_features_backward", "cs_policy_last_error", "cs_store_episodes", "cs_store_episodes_compact", "cs_render_episodes", "cs_coverage_actions", "cs_sweep_episodes", "cs_move_targets", "cs_belief_actions", "cs_plan_actions", "cs_belief_forecast", "cs_plan_forecast_actions", "cs_label_episodes", "cs_episodes_last_error", "cs_epsilon_step",
+           "cs_gru_seq_forward", "cs_gru_seq_backward", "cs_episode_returns", "cs_gae", "cs_ppo_loss", "cs_bc_loss", "cs_learn_last_error"]
 
 
 class CsConfig(C.Structure):
@@ -93,6 +93,13 @@ class CsForecastParams(C.Structure):
     """cs_forecast_params of include/coopsearch.h: the density along the planning horizon (forecast.ForecastAgents computes the fields)."""
     _fields_ = [(k, C.c_int32) for k in ("n_agents", "side", "levels", "mode", "sense16")] + \
                [("dx", C.c_int32 * 16), ("dy", C.c_int32 * 16), ("moves", C.c_int32 * 5), ("reserved", C.c_int32)]
+
+
+class CsLabelParams(C.Structure):
+    """cs_label_params of include/coopsearch.h: an expert relabels recorded episodes (imitate.expert_params computes the fields)."""
+    _fields_ = [(k, C.c_int32) for k in ("expert", "n_agents", "side", "view_range", "keep", "regrow", "lookahead", "state_width", "mode",
+                                         "sense16", "every", "moving")] + \
+               [("dx", C.c_int32 * 16), ("dy", C.c_int32 * 16), ("reserved", C.c_int32)]
 
 
 class CsEpsilon(C.Structure):
@@ -169,6 +176,8 @@ def load():
     L.cs_plan_actions.argtypes = [C.POINTER(CsPlanParams), vp, C.c_int, vp, vp, vp, vp, vp]
     L.cs_belief_forecast.argtypes = [C.POINTER(CsForecastParams), vp, vp, C.c_int, vp, vp]
     L.cs_plan_forecast_actions.argtypes = [C.POINTER(CsPlanParams), vp, C.c_int, vp, vp, vp, vp, vp]
+    L.cs_label_episodes.argtypes = [C.POINTER(CsLabelParams), vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    L.cs_bc_loss.argtypes = [vp] * 4 + [C.c_int64, C.c_int, C.c_int] + [vp] * 4 + [C.c_int64, vp]
     L.cs_policy_pack.argtypes = [vp] * 10 + [C.c_int, C.c_int, vp]
     L.cs_policy_pack_device.argtypes = [vp] * 10 + [C.c_int, C.c_int, vp, vp, vp]
     L.cs_policy_forward.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int,

@@ -33,6 +33,7 @@ namespace {
 #include "gru_seq.h"
 #include "returns.h"
 #include "ppo.h"
+#include "bc_loss.h"
 
 struct PolicyParams {
     int rows, n_agents, n_actions, obs_stride, obs_offset;  // obs row r starts at obs + r*obs_stride + obs_offset (4 floats)
@@ -503,7 +504,7 @@ __global__ __launch_bounds__(KBLOCK) void k_policy_pack(PackParams p) {
 }
 
 thread_local char g_perr[200] = "";
-thread_local char g_lerr[200] = "";   // cs_gru_seq_*, cs_episode_returns, cs_gae, cs_ppo_loss
+thread_local char g_lerr[200] = "";   // cs_gru_seq_*, cs_episode_returns, cs_gae, cs_ppo_loss, cs_bc_loss
 
 // persistent grid: as many blocks as the device holds at once (queried once)
 template <typename K>
@@ -526,6 +527,19 @@ void ppo_launch(int n_actions, dim3 grid, hipStream_t stream, const PpoParams &p
         case 6: hipLaunchKernelGGL((k_ppo_loss<6, FULL>), grid, dim3(PPO_BLOCK), 0, stream, p); break;
         case 7: hipLaunchKernelGGL((k_ppo_loss<7, FULL>), grid, dim3(PPO_BLOCK), 0, stream, p); break;
         default: hipLaunchKernelGGL((k_ppo_loss<8, FULL>), grid, dim3(PPO_BLOCK), 0, stream, p); break;
+    }
+}
+
+// k_bc_loss for the row width at hand (cs_bc_loss has checked 2 <= n_actions <= 8)
+void bc_launch(int n_actions, dim3 grid, hipStream_t stream, const BcParams &p) {
+    switch (n_actions) {
+        case 2: hipLaunchKernelGGL((k_bc_loss<2>), grid, dim3(PPO_BLOCK), 0, stream, p); break;
+        case 3: hipLaunchKernelGGL((k_bc_loss<3>), grid, dim3(PPO_BLOCK), 0, stream, p); break;
+        case 4: hipLaunchKernelGGL((k_bc_loss<4>), grid, dim3(PPO_BLOCK), 0, stream, p); break;
+        case 5: hipLaunchKernelGGL((k_bc_loss<5>), grid, dim3(PPO_BLOCK), 0, stream, p); break;
+        case 6: hipLaunchKernelGGL((k_bc_loss<6>), grid, dim3(PPO_BLOCK), 0, stream, p); break;
+        case 7: hipLaunchKernelGGL((k_bc_loss<7>), grid, dim3(PPO_BLOCK), 0, stream, p); break;
+        default: hipLaunchKernelGGL((k_bc_loss<8>), grid, dim3(PPO_BLOCK), 0, stream, p); break;
     }
 }
 
@@ -825,6 +839,38 @@ int cs_ppo_loss(const float *logits, const float *avail, const int64_t *u, const
             snprintf(g_lerr, sizeof(g_lerr), "cs_ppo_loss: reduction launch failed");
             return CS_E_LAUNCH;
         }
+    }
+    return CS_OK;
+}
+
+// ---- imitation learner: the masked cross-entropy against an expert's labels, its statistics and its gradient (bc_loss.h) -----
+int cs_bc_loss(const float *logits, const float *avail, const int64_t *labels, const float *mask, int64_t rows, int n_agents,
+               int n_actions, const float *inv_count_dev, float *dlogits_out, float *stats_out, float *scratch_dev,
+               int64_t scratch_floats, void *stream) {
+    const int64_t max_rows = (int64_t)0x7fffffff / CS_PPO_BLOCK * CS_PPO_BLOCK;   // the grid's x extent is an int
+    if (!logits || !avail || !labels || !mask || !inv_count_dev || !dlogits_out || !stats_out || !scratch_dev || rows < 1 ||
+        rows > max_rows || n_agents < 1 || rows % n_agents != 0 || n_actions < 2 || n_actions > 8) {
+        snprintf(g_lerr, sizeof(g_lerr), "cs_bc_loss: bad argument (rows = %lld, n_agents = %d, n_actions = %d: rows a multiple of "
+                 "n_agents, 2 to 8 actions; no pointer may be null)", (long long)rows, n_agents, n_actions);
+        return CS_E_ARG;
+    }
+    const int blocks = (int)((rows + CS_PPO_BLOCK - 1) / CS_PPO_BLOCK);
+    if (scratch_floats < (int64_t)blocks * 3) {
+        snprintf(g_lerr, sizeof(g_lerr), "cs_bc_loss: scratch holds %lld floats, %lld needed (3 per CS_PPO_BLOCK rows)",
+                 (long long)scratch_floats, (long long)blocks * 3);
+        return CS_E_ARG;
+    }
+    const BcParams p{logits, avail, labels, mask, inv_count_dev, dlogits_out, scratch_dev, (long long)rows, n_agents};
+    bc_launch(n_actions, dim3(blocks), (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_lerr, sizeof(g_lerr), "cs_bc_loss: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    const BcFinishParams f{scratch_dev, inv_count_dev, stats_out, blocks};
+    hipLaunchKernelGGL(k_bc_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, f);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_lerr, sizeof(g_lerr), "cs_bc_loss: reduction launch failed");
+        return CS_E_LAUNCH;
     }
     return CS_OK;
 }

@@ -963,6 +963,92 @@ void ppo_loss(const Tensor &logits, const Tensor &avail, const Tensor &u, const 
     TORCH_CHECK(rc == CS_OK, cs_learn_last_error());
 }
 
+// ---- imitation learner: the masked cross-entropy against an expert's labels (cs_bc_loss) -----------------------------------------
+void bc_loss(const Tensor &logits, const Tensor &avail, const Tensor &labels, const Tensor &mask, int64_t rows, int64_t n_agents,
+             int64_t n_actions, const Tensor &inv_count, Tensor dlogits, Tensor stats, Tensor scratch) {
+    TORCH_CHECK(rows >= 1 && n_agents >= 1 && rows % n_agents == 0, "coopsearch: bc_loss: rows must be a positive multiple of n_agents");
+    TORCH_CHECK(n_actions >= 2 && n_actions <= 8, "coopsearch: bc_loss: n_actions must be 2 to 8");
+    TORCH_CHECK(logits.is_cuda(), "coopsearch: bc_loss: logits must be a GPU tensor");
+    check_f32(logits, "logits", rows * n_actions, logits);
+    check_f32(avail, "avail", rows * n_actions, logits);
+    check_dev(labels, "labels", at::kLong, rows, logits);
+    check_f32(mask, "mask", rows / n_agents, logits);
+    check_f32(inv_count, "inv_count", 1, logits);
+    check_f32(dlogits, "dlogits", rows * n_actions, logits);
+    check_f32(stats, "stats", 3, logits);
+    check_f32(scratch, "scratch", -1, logits);
+    const int rc = cs_bc_loss(logits.data_ptr<float>(), avail.data_ptr<float>(), labels.data_ptr<int64_t>(), mask.data_ptr<float>(), rows,
+                              (int)n_agents, (int)n_actions, inv_count.data_ptr<float>(), dlogits.data_ptr<float>(),
+                              stats.data_ptr<float>(), scratch.data_ptr<float>(), scratch.numel(), stream_of(logits));
+    TORCH_CHECK(rc == CS_OK, cs_learn_last_error());
+}
+
+// ---- an expert relabels recorded episodes (cs_label_episodes): s [E, T, S >= 4n] float32 and lens [E] int32 (in), labels [E, T, n]
+// int64, grid_out [E, side * side] int32 and prev_out [E, 8, 2] int32 (out; the last two optional).  Integers and shapes first (nothing
+// is dereferenced), then the tensors.
+void label_episodes(const Tensor &s, const Tensor &lens, Tensor labels, c10::optional<Tensor> grid_out, c10::optional<Tensor> prev_out,
+                    int64_t expert, int64_t n_agents, int64_t side, int64_t view_range, int64_t keep, int64_t regrow, int64_t lookahead,
+                    int64_t mode, int64_t sense16, int64_t every, int64_t moving, at::IntArrayRef dx, at::IntArrayRef dy) {
+    auto has = [](const c10::optional<Tensor> &t) { return t.has_value() && t->defined(); };
+    TORCH_CHECK(expert == 0 || expert == 1, "coopsearch: label_episodes: expert must be 0 (coverage) or 1 (belief), got ", expert);
+    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: label_episodes: n_agents must be 1..8, got ", n_agents);
+    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: label_episodes: side must be 1..", CS_MAX_MAP, ", got ", side);
+    TORCH_CHECK(view_range >= 0 && view_range <= CS_MAX_MAP, "coopsearch: label_episodes: view_range must be 0..", CS_MAX_MAP, ", got ",
+                view_range);
+    TORCH_CHECK(keep >= 0 && keep <= 65536, "coopsearch: label_episodes: keep must be 0..65536, got ", keep);
+    TORCH_CHECK(regrow >= 1 && regrow <= 16, "coopsearch: label_episodes: regrow must be 1..16, got ", regrow);
+    TORCH_CHECK(lookahead >= 0 && lookahead <= side, "coopsearch: label_episodes: lookahead must be 0..side, got ", lookahead);
+    TORCH_CHECK(mode == CS_MOTION_WALK || mode == CS_MOTION_EVADE, "coopsearch: label_episodes: mode must be 0 (walk) or 1 (evade), got ", mode);
+    TORCH_CHECK(sense16 >= 0 && sense16 <= 32 * CS_MAX_MAP, "coopsearch: label_episodes: sense16 must be 0..", 32 * CS_MAX_MAP, ", got ", sense16);
+    TORCH_CHECK(every >= 1 && every <= INT32_MAX, "coopsearch: label_episodes: every must be >= 1, got ", every);
+    TORCH_CHECK(moving == 0 || moving == 1, "coopsearch: label_episodes: moving must be 0 or 1, got ", moving);
+    TORCH_CHECK(dx.size() == 16 && dy.size() == 16, "coopsearch: label_episodes: dx and dy must hold 16 integers each");
+    for (int k = 0; k < 16; k++)
+        TORCH_CHECK(dx[k] >= -16 * CS_MAX_MAP && dx[k] <= 16 * CS_MAX_MAP && dy[k] >= -16 * CS_MAX_MAP && dy[k] <= 16 * CS_MAX_MAP,
+                    "coopsearch: label_episodes: dx and dy must be -1024..1024, got ", dx[k], " and ", dy[k], " at ", k);
+    TORCH_CHECK(s.dim() == 3 && s.size(0) >= 1 && s.size(0) <= INT32_MAX && s.size(1) >= 1 && s.size(1) <= INT32_MAX &&
+                    s.size(2) >= 4 * n_agents && s.size(2) <= INT32_MAX,
+                "coopsearch: label_episodes: s must be [E, T, S] with E >= 1, T >= 1 and S >= 4 n_agents = ", 4 * n_agents);
+    const int64_t E = s.size(0), T = s.size(1), S = s.size(2);
+    TORCH_CHECK(lens.dim() == 1 && lens.size(0) == E, "coopsearch: label_episodes: lens must be [", E, "]");
+    TORCH_CHECK(labels.dim() == 3 && labels.size(0) == E && labels.size(1) == T && labels.size(2) == n_agents,
+                "coopsearch: label_episodes: labels must be [", E, ", ", T, ", ", n_agents, "]");
+    if (has(grid_out))
+        TORCH_CHECK(grid_out->dim() == 2 && grid_out->size(0) == E && grid_out->size(1) == side * side,
+                    "coopsearch: label_episodes: grid_out must be [", E, ", ", side * side, "]");
+    if (has(prev_out)) {
+        TORCH_CHECK(expert == 1, "coopsearch: label_episodes: prev_out is the belief expert's (the coverage expert keeps no positions)");
+        TORCH_CHECK(prev_out->dim() == 3 && prev_out->size(0) == E && prev_out->size(1) == CS_MAX_AGENTS && prev_out->size(2) == 2,
+                    "coopsearch: label_episodes: prev_out must be [", E, ", ", CS_MAX_AGENTS, ", 2]");
+    }
+    TORCH_CHECK(s.is_cuda(), "coopsearch: label_episodes: s must be a GPU tensor");
+    check_f32(s, "s", E * T * S, s);
+    check_dev(lens, "lens", at::kInt, E, s);
+    check_dev(labels, "labels", at::kLong, E * T * n_agents, s);
+    if (has(grid_out)) check_dev(*grid_out, "grid_out", at::kInt, E * side * side, s);
+    if (has(prev_out)) check_dev(*prev_out, "prev_out", at::kInt, E * CS_MAX_AGENTS * 2, s);
+    cs_label_params p{};
+    p.expert = (int32_t)expert;
+    p.n_agents = (int32_t)n_agents;
+    p.side = (int32_t)side;
+    p.view_range = (int32_t)view_range;
+    p.keep = (int32_t)keep;
+    p.regrow = (int32_t)regrow;
+    p.lookahead = (int32_t)lookahead;
+    p.state_width = (int32_t)S;
+    p.mode = (int32_t)mode;
+    p.sense16 = (int32_t)sense16;
+    p.every = (int32_t)every;
+    p.moving = (int32_t)moving;
+    for (int k = 0; k < 16; k++) {
+        p.dx[k] = (int32_t)dx[k];
+        p.dy[k] = (int32_t)dy[k];
+    }
+    const int rc = cs_label_episodes(&p, s.data_ptr<float>(), (int)E, (int)T, lens.data_ptr<int32_t>(), labels.data_ptr<int64_t>(),
+                                     opt_ptr<int32_t>(grid_out), opt_ptr<int32_t>(prev_out), stream_of(s));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
 }  // namespace
 
 TORCH_LIBRARY(coopsearch, m) {
@@ -1042,4 +1128,9 @@ TORCH_LIBRARY(coopsearch, m) {
     m.def("ppo_loss(Tensor logits, Tensor avail, Tensor u, Tensor? old_logp, Tensor? adv, Tensor mask, int rows, int n_agents, "
           "int n_actions, float clip, float ent_coef, float epsilon, Tensor? epsilon_t, Tensor? inv_count, Tensor(a!)? dlogits, "
           "Tensor(b!)? logp_out, Tensor(c!)? stats, Tensor(d!)? scratch) -> ()", &ppo_loss);
+    m.def("bc_loss(Tensor logits, Tensor avail, Tensor labels, Tensor mask, int rows, int n_agents, int n_actions, Tensor inv_count, "
+          "Tensor(a!) dlogits, Tensor(b!) stats, Tensor(c!) scratch) -> ()", &bc_loss);
+    m.def("label_episodes(Tensor s, Tensor lens, Tensor(a!) labels, Tensor(b!)? grid_out, Tensor(c!)? prev_out, int expert, int n_agents, "
+          "int side, int view_range, int keep, int regrow, int lookahead, int mode, int sense16, int every, int moving, int[] dx, "
+          "int[] dy) -> ()", &label_episodes);
 }

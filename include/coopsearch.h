@@ -41,7 +41,8 @@ extern "C" {
                               cs_store_episodes_compact, then cs_snapshot_bytes, cs_snapshot and cs_restore, then cs_render_params and
                               cs_render_episodes, then cs_gae and cs_ppo_loss, then cs_coverage_params and cs_coverage_actions, then cs_sweep_params and cs_sweep_episodes, then
                               cs_motion_params and cs_move_targets, then cs_belief_params and cs_belief_actions,
-                              then cs_plan_params and cs_plan_actions, then cs_forecast_params, cs_belief_forecast and cs_plan_forecast_actions
+                              then cs_plan_params and cs_plan_actions, then cs_forecast_params, cs_belief_forecast and cs_plan_forecast_actions,
+                              then cs_label_params, cs_label_episodes and cs_bc_loss
                               (no existing export or struct changed: a version-7 caller works unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
@@ -682,6 +683,43 @@ int cs_belief_forecast(const cs_forecast_params *p, const int32_t *grid_dev, con
 int cs_plan_forecast_actions(const cs_plan_params *p, const float *state_dev, int B, const int32_t *stack_dev, int64_t *actions_dev,
                              int64_t *plans_dev, int64_t *scores_dev, void *stream);
 
+/* ---- an expert relabels a recorded batch of episodes, one launch per batch -------------------
+ * Imitation learning (DAgger) asks what cs_coverage_actions or cs_belief_actions WOULD have done in every state another policy
+ * reached.  Those experts decide from (state row, t) and their own grid alone, so walking the recorded rows s[e][0..T-1] of every
+ * episode in order, from a fresh grid (65536 everywhere, stored positions 0), gives what shadowing the flight would have given.
+ * Row t of a belief expert is cs_belief_actions with moved = (moving && t > 0 && (t - 1) % every == 0); row t of a coverage expert is
+ * cs_coverage_actions.  Only the rows t < lens[e] are walked (lens[e] is read clamped to 0..T): the rows behind them are never read,
+ * their labels are 0, and the episode's grid and positions stay as its last live row left them.  DEFINED by
+ * imitate.label_episodes_torch (a loop over the two definitions); the kernel reproduces labels, grid_out and prev_out element for
+ * element, with the expert's grid in LDS from the first row to the last.
+ *   s_dev       float [E][T][state_width], in (the first 4 n_agents floats of a row are read)      lens_dev  int32 [E], in
+ *   labels_dev  int64 [E][T][n_agents], out    grid_out_dev  int32 [E][side * side], out, or NULL
+ *   prev_out_dev  int32 [E][8][2], out, or NULL; belief only (slots >= n_agents are written as 0) */
+typedef struct cs_label_params {
+    int32_t expert;       /* 0: cs_coverage_actions' policy, 1: cs_belief_actions' */
+    int32_t n_agents;     /* 1..8 */
+    int32_t side;         /* map_size: cells per side, 1..CS_MAX_MAP */
+    int32_t view_range;   /* sensor radius in cells, 0..CS_MAX_MAP */
+    int32_t keep;         /* rint((1 - detect_prob) * 65536), 0..65536 */
+    int32_t regrow;       /* regrowth shift, 1..16 (coverage; checked, then unused, for belief) */
+    int32_t lookahead;    /* distance of the look-ahead point in cells, 0..side */
+    int32_t state_width;  /* floats per state row, >= 4 n_agents */
+    int32_t mode;         /* belief: the motion model, CS_MOTION_WALK or CS_MOTION_EVADE */
+    int32_t sense16;      /* belief: rint(16 sense), 0..2048 (evade only) */
+    int32_t every;        /* belief: env steps between two moves of the targets, >= 1 */
+    int32_t moving;       /* belief: 1 if the targets move at all (speed > 0), else 0 */
+    int32_t dx[16];       /* belief: rint(16 speed cos(2 pi k / 16)), -1024..1024 */
+    int32_t dy[16];       /* belief: rint(16 speed sin(2 pi k / 16)), -1024..1024 */
+    int32_t reserved;     /* must be 0 (CS_E_CONFIG otherwise) */
+} cs_label_params;
+
+/* One launch on `stream`, one workgroup per episode, atomics on LDS only (integer: the result does not depend on their order), no
+ * synchronisation.  CS_E_CONFIG (before any launch) for a field out of range, a non-zero `reserved`, a NULL or misaligned pointer
+ * (grid_out_dev and prev_out_dev may be NULL; prev_out_dev must be NULL for the coverage expert), E < 1 or T < 1.  The message is
+ * cs_episodes_last_error()'s. */
+int cs_label_episodes(const cs_label_params *p, const float *s_dev, int E, int T, const int32_t *lens_dev, int64_t *labels_dev,
+                      int32_t *grid_out_dev, int32_t *prev_out_dev, void *stream);
+
 /* ---- QMIX learner: the GRU recurrence of the agent network over T steps, forward and backward ---------------------
  * Replaces the per-transition unroll of policy/qmix.py:160-182 (get_q_values) over network/base_net.py:40-46
  * (GRUCell(64)) and autograd's walk back through it: ONE launch for all T steps of all rows, whatever T is.  The batched
@@ -745,6 +783,21 @@ int cs_ppo_loss(const float *logits, const float *avail, const int64_t *u, const
                 const float *mask, int64_t rows, int n_agents, int n_actions, float clip, float ent_coef, float epsilon,
                 const float *epsilon_dev, const float *inv_count_dev, float *dlogits_out, float *logp_out, float *stats_out,
                 float *scratch_dev, int64_t scratch_floats, void *stream);
+/* Imitation learner (imitate.ImitationLearner): the masked cross-entropy between the actor's action probabilities and an expert's
+ * labels, its statistics and its gradient with respect to the logits, in one pass over the rows = E * T * n_agents rows (row rho
+ * belongs to step rho / n_agents).  logits, avail [rows][n_actions] float32 (2 to 8 actions), labels [rows] int64, mask
+ * [rows / n_agents]; inv_count_dev[0] = 1 / (n_agents * sum(mask)), a device scalar.  Per row with mask != 0: p = the reference
+ * actors' action probabilities with epsilon 0 (softmax, unavailable actions zeroed, renormalised), ce = -log p[label].
+ *   dlogits_out [rows][n_actions] = d(inv_count * sum mask ce) / dlogits = mask inv_count (p - onehot(label))
+ *   stats_out [3] = (loss = mean ce, agreement = mean [argmax p == label], the lowest index on ties, mean entropy -sum p log p),
+ *     means over the live rows.
+ * A live row whose label is unavailable (or outside 0..n_actions - 1) adds no loss and no gradient and counts as a miss.  Rows with
+ * mask == 0 give zeros everywhere, whatever their other inputs hold.  scratch_dev: scratch_floats >= 3 * ceil(rows /
+ * CS_PPO_BLOCK) floats (one partial per block; a second one-block launch adds them in a fixed order).  No atomics: reruns are
+ * bit-identical.  CS_E_ARG (before any launch) for a NULL pointer or a count out of range; the message is cs_learn_last_error()'s. */
+int cs_bc_loss(const float *logits, const float *avail, const int64_t *labels, const float *mask, int64_t rows, int n_agents,
+               int n_actions, const float *inv_count_dev, float *dlogits_out, float *stats_out, float *scratch_dev,
+               int64_t scratch_floats, void *stream);
 const char *cs_learn_last_error(void);
 
 #ifdef __cplusplus
