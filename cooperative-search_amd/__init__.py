@@ -27,6 +27,8 @@ from .plan import PlanAgents, plan_actions_torch  # noqa: F401
 from .forecast import ForecastAgents, forecast_torch, plan_forecast_actions_torch  # noqa: F401
 from .imitate import BCLoss, ExpertParams, ImitationLearner, LabelledRing, bc_loss_torch, distil, expert_params, get_bc_args  # noqa: F401
 from .imitate import label_episodes, label_episodes_hip, label_episodes_torch  # noqa: F401
+from .gridobs import FeatureRing, GridAgents, GridImitationLearner, distil_grid, feature_episodes, feature_episodes_hip  # noqa: F401
+from .gridobs import feature_episodes_torch, grid_features, grid_features_hip, grid_features_torch  # noqa: F401
 from .render import RenderSpec, episode_tables, render_episodes, render_episodes_torch, write_frames  # noqa: F401
 
 __all__ = ["BatchedFlightEnv", "FlightSearchEnvEasy", "FlightSearchEnv", "load_targets", "default_circle_dict",

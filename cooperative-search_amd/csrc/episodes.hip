@@ -158,6 +158,7 @@ __global__ __launch_bounds__(256) void k_compact_small(CompactParams p) {
 #include "plan.h"     // k_plan_actions: a receding-horizon sequence search over a base policy's grid (cs_plan_actions)
 #include "forecast.h" // k_belief_forecast, k_plan_forecast_actions: the density along the horizon and the search scored on it
 #include "label.h"    // k_label_episodes: an expert of coverage.h / belief.h relabels a recorded batch in one launch (cs_label_episodes)
+#include "gridobs.h"  // k_grid_features, k_feature_episodes: sixteen floats per agent from a policy's grid (cs_grid_features, cs_feature_episodes)
 
 thread_local char g_eerr[160] = "";
 
@@ -533,6 +534,92 @@ int cs_label_episodes(const cs_label_params *p, const float *s_dev, int E, int T
     hipLaunchKernelGGL(k_label_episodes, dim3((unsigned)E), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
     if (hipGetLastError() != hipSuccess) {
         snprintf(g_eerr, sizeof(g_eerr), "cs_label_episodes: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    return CS_OK;
+}
+
+int cs_grid_features(const cs_grid_params *p, const float *state_dev, int B, const int32_t *grid_dev, float *feat_dev, void *stream) {
+    const char *bad = nullptr;
+    if (!p || !state_dev || !grid_dev || !feat_dev) bad = "a NULL pointer";
+    else if (B < 1) bad = "B must be >= 1";
+    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
+    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
+    else if (p->view_range < 0 || p->view_range > CS_MAX_MAP) bad = "view_range must be 0..64";
+    else if (p->lookahead < 0 || p->lookahead > p->side) bad = "lookahead must be 0..side";
+    else if (p->state_width < 4 * p->n_agents) bad = "state_width must be at least 4 n_agents";
+    else if (p->reserved != 0) bad = "reserved must be 0";
+    else if ((uintptr_t)grid_dev % 4 != 0 || (uintptr_t)state_dev % 4 != 0 || (uintptr_t)feat_dev % 4 != 0)
+        bad = "a pointer is not aligned to its element size";
+    if (bad) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_grid_features: %s", bad);
+        return CS_E_CONFIG;
+    }
+    const GridObsArgs a{state_dev, grid_dev, feat_dev, p->n_agents, p->side, p->state_width, 16 * p->view_range, 16 * p->lookahead};
+    hipLaunchKernelGGL(k_grid_features, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_grid_features: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    return CS_OK;
+}
+
+int cs_feature_episodes(const cs_label_params *p, const float *s_dev, int E, int T, const int32_t *lens_dev, float *feat_dev,
+                        int64_t *labels_dev, int32_t *grid_out_dev, int32_t *prev_out_dev, void *stream) {
+    const char *bad = nullptr;
+    if (!p || !s_dev || !lens_dev || !feat_dev) bad = "a NULL pointer";
+    else if (E < 1 || T < 1) bad = "E and T must be >= 1";
+    else if (p->expert != LABEL_COVERAGE && p->expert != LABEL_BELIEF) bad = "expert must be 0 (coverage) or 1 (belief)";
+    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
+    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
+    else if (p->view_range < 0 || p->view_range > CS_MAX_MAP) bad = "view_range must be 0..64";
+    else if (p->keep < 0 || p->keep > 65536) bad = "keep must be 0..65536";
+    else if (p->regrow < 1 || p->regrow > 16) bad = "regrow must be 1..16";
+    else if (p->lookahead < 0 || p->lookahead > p->side) bad = "lookahead must be 0..side";
+    else if (p->state_width < 4 * p->n_agents) bad = "state_width must be at least 4 n_agents";
+    else if (p->mode != CS_MOTION_WALK && p->mode != CS_MOTION_EVADE) bad = "mode must be CS_MOTION_WALK or CS_MOTION_EVADE";
+    else if (p->sense16 < 0 || p->sense16 > 32 * CS_MAX_MAP) bad = "sense16 must be 0..2048";
+    else if (p->every < 1) bad = "every must be >= 1";
+    else if (p->moving != 0 && p->moving != 1) bad = "moving must be 0 or 1";
+    else if (p->reserved != 0) bad = "reserved must be 0";
+    else if (p->expert == LABEL_COVERAGE && prev_out_dev) bad = "prev_out_dev is the belief filter's (the coverage filter keeps no positions)";
+    else if ((uintptr_t)s_dev % 4 != 0 || (uintptr_t)lens_dev % 4 != 0 || (uintptr_t)feat_dev % 4 != 0 || (uintptr_t)labels_dev % 8 != 0 ||
+             (uintptr_t)grid_out_dev % 4 != 0 || (uintptr_t)prev_out_dev % 4 != 0)
+        bad = "a pointer is not aligned to its element size";
+    for (int k = 0; !bad && k < 16; k++)
+        if (p->dx[k] < -16 * CS_MAX_MAP || p->dx[k] > 16 * CS_MAX_MAP || p->dy[k] < -16 * CS_MAX_MAP || p->dy[k] > 16 * CS_MAX_MAP)
+            bad = "dx and dy must be -1024..1024";
+    if (bad) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_feature_episodes: %s", bad);
+        return CS_E_CONFIG;
+    }
+    const int cells = p->side * p->side;
+    FeatArgs f{};
+    LabelArgs &a = f.l;
+    a.b.c = CoverageArgs{s_dev, nullptr, labels_dev, p->n_agents, p->side, p->state_width, 16 * p->view_range, p->keep, p->regrow,
+                         16 * p->lookahead, (cells % 4 == 0 && (uintptr_t)grid_out_dev % 16 == 0) ? 1 : 0};
+    a.b.prev = nullptr;
+    a.b.mode = p->mode;
+    a.b.moved = 0;
+    a.b.sense2 = (unsigned)p->sense16 * (unsigned)p->sense16;
+    for (int k = 0; k < 16; k++) {
+        a.b.dx[k] = p->dx[k];
+        a.b.dy[k] = p->dy[k];
+    }
+    a.lens = lens_dev;
+    a.grid_out = grid_out_dev;
+    a.prev_out = prev_out_dev;
+    a.T = T;
+    a.expert = p->expert;
+    a.every = p->every;
+    a.moving = p->moving;
+    a.svec = (p->state_width % 4 == 0 && (uintptr_t)s_dev % 16 == 0) ? 1 : 0;
+    a.lvec = (uintptr_t)labels_dev % 16 == 0 ? 1 : 0;
+    f.feat = feat_dev;
+    f.fvec = (uintptr_t)feat_dev % 16 == 0 ? 1 : 0;
+    hipLaunchKernelGGL(k_feature_episodes, dim3((unsigned)E), dim3(COV_THREADS), 0, (hipStream_t)stream, f);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_feature_episodes: kernel launch failed");
         return CS_E_LAUNCH;
     }
     return CS_OK;

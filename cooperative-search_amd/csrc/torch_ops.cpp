@@ -1049,6 +1049,102 @@ void label_episodes(const Tensor &s, const Tensor &lens, Tensor labels, c10::opt
     TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
 }
 
+// ---- grid observations of one decision (cs_grid_features): state [B, S >= 4n] float32 and grid [B, side * side] int32 (in, read
+// only), feat [B, n, 16] float32 (out).  Integers and shapes first (nothing is dereferenced), then the tensors.
+void grid_features(const Tensor &state, const Tensor &grid, Tensor feat, int64_t n_agents, int64_t side, int64_t view_range,
+                   int64_t lookahead) {
+    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: grid_features: n_agents must be 1..8, got ", n_agents);
+    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: grid_features: side must be 1..", CS_MAX_MAP, ", got ", side);
+    TORCH_CHECK(view_range >= 0 && view_range <= CS_MAX_MAP, "coopsearch: grid_features: view_range must be 0..", CS_MAX_MAP, ", got ",
+                view_range);
+    TORCH_CHECK(lookahead >= 0 && lookahead <= side, "coopsearch: grid_features: lookahead must be 0..side, got ", lookahead);
+    TORCH_CHECK(state.dim() == 2 && state.size(0) >= 1 && state.size(0) <= INT32_MAX && state.size(1) >= 4 * n_agents &&
+                    state.size(1) <= INT32_MAX,
+                "coopsearch: grid_features: state must be [B, S] with B >= 1 and S >= 4 n_agents = ", 4 * n_agents);
+    const int64_t B = state.size(0), S = state.size(1);
+    TORCH_CHECK(grid.dim() == 2 && grid.size(0) == B && grid.size(1) == side * side, "coopsearch: grid_features: grid must be [", B, ", ",
+                side * side, "]");
+    TORCH_CHECK(feat.dim() == 3 && feat.size(0) == B && feat.size(1) == n_agents && feat.size(2) == 16,
+                "coopsearch: grid_features: feat must be [", B, ", ", n_agents, ", 16]");
+    TORCH_CHECK(state.is_cuda(), "coopsearch: grid_features: state must be a GPU tensor");
+    check_f32(state, "state", B * S, state);
+    check_dev(grid, "grid", at::kInt, B * side * side, state);
+    check_f32(feat, "feat", B * n_agents * 16, state);
+    const cs_grid_params p{(int32_t)n_agents, (int32_t)side, (int32_t)view_range, (int32_t)lookahead, (int32_t)S, 0};
+    const int rc = cs_grid_features(&p, state.data_ptr<float>(), (int)B, grid.data_ptr<int32_t>(), feat.data_ptr<float>(), stream_of(state));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
+// ---- grid observations of recorded episodes (cs_feature_episodes): label_episodes' tensors and integers plus feat [E, T, n, 16]
+// float32 (out); labels is optional here.  Integers and shapes first (nothing is dereferenced), then the tensors.
+void feature_episodes(const Tensor &s, const Tensor &lens, Tensor feat, c10::optional<Tensor> labels, c10::optional<Tensor> grid_out,
+                      c10::optional<Tensor> prev_out, int64_t expert, int64_t n_agents, int64_t side, int64_t view_range, int64_t keep,
+                      int64_t regrow, int64_t lookahead, int64_t mode, int64_t sense16, int64_t every, int64_t moving, at::IntArrayRef dx,
+                      at::IntArrayRef dy) {
+    auto has = [](const c10::optional<Tensor> &t) { return t.has_value() && t->defined(); };
+    TORCH_CHECK(expert == 0 || expert == 1, "coopsearch: feature_episodes: expert must be 0 (coverage) or 1 (belief), got ", expert);
+    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: feature_episodes: n_agents must be 1..8, got ", n_agents);
+    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: feature_episodes: side must be 1..", CS_MAX_MAP, ", got ", side);
+    TORCH_CHECK(view_range >= 0 && view_range <= CS_MAX_MAP, "coopsearch: feature_episodes: view_range must be 0..", CS_MAX_MAP, ", got ",
+                view_range);
+    TORCH_CHECK(keep >= 0 && keep <= 65536, "coopsearch: feature_episodes: keep must be 0..65536, got ", keep);
+    TORCH_CHECK(regrow >= 1 && regrow <= 16, "coopsearch: feature_episodes: regrow must be 1..16, got ", regrow);
+    TORCH_CHECK(lookahead >= 0 && lookahead <= side, "coopsearch: feature_episodes: lookahead must be 0..side, got ", lookahead);
+    TORCH_CHECK(mode == CS_MOTION_WALK || mode == CS_MOTION_EVADE, "coopsearch: feature_episodes: mode must be 0 (walk) or 1 (evade), got ", mode);
+    TORCH_CHECK(sense16 >= 0 && sense16 <= 32 * CS_MAX_MAP, "coopsearch: feature_episodes: sense16 must be 0..", 32 * CS_MAX_MAP, ", got ", sense16);
+    TORCH_CHECK(every >= 1 && every <= INT32_MAX, "coopsearch: feature_episodes: every must be >= 1, got ", every);
+    TORCH_CHECK(moving == 0 || moving == 1, "coopsearch: feature_episodes: moving must be 0 or 1, got ", moving);
+    TORCH_CHECK(dx.size() == 16 && dy.size() == 16, "coopsearch: feature_episodes: dx and dy must hold 16 integers each");
+    for (int k = 0; k < 16; k++)
+        TORCH_CHECK(dx[k] >= -16 * CS_MAX_MAP && dx[k] <= 16 * CS_MAX_MAP && dy[k] >= -16 * CS_MAX_MAP && dy[k] <= 16 * CS_MAX_MAP,
+                    "coopsearch: feature_episodes: dx and dy must be -1024..1024, got ", dx[k], " and ", dy[k], " at ", k);
+    TORCH_CHECK(s.dim() == 3 && s.size(0) >= 1 && s.size(0) <= INT32_MAX && s.size(1) >= 1 && s.size(1) <= INT32_MAX &&
+                    s.size(2) >= 4 * n_agents && s.size(2) <= INT32_MAX,
+                "coopsearch: feature_episodes: s must be [E, T, S] with E >= 1, T >= 1 and S >= 4 n_agents = ", 4 * n_agents);
+    const int64_t E = s.size(0), T = s.size(1), S = s.size(2);
+    TORCH_CHECK(lens.dim() == 1 && lens.size(0) == E, "coopsearch: feature_episodes: lens must be [", E, "]");
+    TORCH_CHECK(feat.dim() == 4 && feat.size(0) == E && feat.size(1) == T && feat.size(2) == n_agents && feat.size(3) == 16,
+                "coopsearch: feature_episodes: feat must be [", E, ", ", T, ", ", n_agents, ", 16]");
+    if (has(labels))
+        TORCH_CHECK(labels->dim() == 3 && labels->size(0) == E && labels->size(1) == T && labels->size(2) == n_agents,
+                    "coopsearch: feature_episodes: labels must be [", E, ", ", T, ", ", n_agents, "]");
+    if (has(grid_out))
+        TORCH_CHECK(grid_out->dim() == 2 && grid_out->size(0) == E && grid_out->size(1) == side * side,
+                    "coopsearch: feature_episodes: grid_out must be [", E, ", ", side * side, "]");
+    if (has(prev_out)) {
+        TORCH_CHECK(expert == 1, "coopsearch: feature_episodes: prev_out is the belief filter's (the coverage filter keeps no positions)");
+        TORCH_CHECK(prev_out->dim() == 3 && prev_out->size(0) == E && prev_out->size(1) == CS_MAX_AGENTS && prev_out->size(2) == 2,
+                    "coopsearch: feature_episodes: prev_out must be [", E, ", ", CS_MAX_AGENTS, ", 2]");
+    }
+    TORCH_CHECK(s.is_cuda(), "coopsearch: feature_episodes: s must be a GPU tensor");
+    check_f32(s, "s", E * T * S, s);
+    check_dev(lens, "lens", at::kInt, E, s);
+    check_f32(feat, "feat", E * T * n_agents * 16, s);
+    if (has(labels)) check_dev(*labels, "labels", at::kLong, E * T * n_agents, s);
+    if (has(grid_out)) check_dev(*grid_out, "grid_out", at::kInt, E * side * side, s);
+    if (has(prev_out)) check_dev(*prev_out, "prev_out", at::kInt, E * CS_MAX_AGENTS * 2, s);
+    cs_label_params p{};
+    p.expert = (int32_t)expert;
+    p.n_agents = (int32_t)n_agents;
+    p.side = (int32_t)side;
+    p.view_range = (int32_t)view_range;
+    p.keep = (int32_t)keep;
+    p.regrow = (int32_t)regrow;
+    p.lookahead = (int32_t)lookahead;
+    p.state_width = (int32_t)S;
+    p.mode = (int32_t)mode;
+    p.sense16 = (int32_t)sense16;
+    p.every = (int32_t)every;
+    p.moving = (int32_t)moving;
+    for (int k = 0; k < 16; k++) {
+        p.dx[k] = (int32_t)dx[k];
+        p.dy[k] = (int32_t)dy[k];
+    }
+    const int rc = cs_feature_episodes(&p, s.data_ptr<float>(), (int)E, (int)T, lens.data_ptr<int32_t>(), feat.data_ptr<float>(),
+                                       opt_ptr<int64_t>(labels), opt_ptr<int32_t>(grid_out), opt_ptr<int32_t>(prev_out), stream_of(s));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
 }  // namespace
 
 TORCH_LIBRARY(coopsearch, m) {
@@ -1133,4 +1229,9 @@ TORCH_LIBRARY(coopsearch, m) {
     m.def("label_episodes(Tensor s, Tensor lens, Tensor(a!) labels, Tensor(b!)? grid_out, Tensor(c!)? prev_out, int expert, int n_agents, "
           "int side, int view_range, int keep, int regrow, int lookahead, int mode, int sense16, int every, int moving, int[] dx, "
           "int[] dy) -> ()", &label_episodes);
+    m.def("grid_features(Tensor state, Tensor grid, Tensor(a!) feat, int n_agents, int side, int view_range, int lookahead) -> ()",
+          &grid_features);
+    m.def("feature_episodes(Tensor s, Tensor lens, Tensor(a!) feat, Tensor(b!)? labels, Tensor(c!)? grid_out, Tensor(d!)? prev_out, "
+          "int expert, int n_agents, int side, int view_range, int keep, int regrow, int lookahead, int mode, int sense16, int every, "
+          "int moving, int[] dx, int[] dy) -> ()", &feature_episodes);
 }

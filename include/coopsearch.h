@@ -42,7 +42,8 @@ extern "C" {
                               cs_render_episodes, then cs_gae and cs_ppo_loss, then cs_coverage_params and cs_coverage_actions, then cs_sweep_params and cs_sweep_episodes, then
                               cs_motion_params and cs_move_targets, then cs_belief_params and cs_belief_actions,
                               then cs_plan_params and cs_plan_actions, then cs_forecast_params, cs_belief_forecast and cs_plan_forecast_actions,
-                              then cs_label_params, cs_label_episodes and cs_bc_loss
+                              then cs_label_params, cs_label_episodes and cs_bc_loss, then cs_grid_params, cs_grid_features and
+                              cs_feature_episodes
                               (no existing export or struct changed: a version-7 caller works unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
@@ -719,6 +720,37 @@ typedef struct cs_label_params {
  * cs_episodes_last_error()'s. */
 int cs_label_episodes(const cs_label_params *p, const float *s_dev, int E, int T, const int32_t *lens_dev, int64_t *labels_dev,
                       int32_t *grid_out_dev, int32_t *prev_out_dev, void *stream);
+
+/* ---- grid observations: sixteen floats per agent from the grid of a coverage or belief policy ---
+ * The agent network observes (x, y, cos, sin); the search policies decide from their grid.  These two calls summarise the grid
+ * for the network: per agent, probe k = 8 ring + b (ring 0..1, b 0..7) lies {1, 3}[ring] * lookahead cells along the heading turned
+ * by {0, 1, 35, 4, 32, 9, 27, 18}[b] * pi / 18, clamped to the map as cs_coverage_actions' look-ahead points are (probes 0, 1, 2 ARE
+ * those points); sum_k is the sum of clamp(cell, 0, 2^19) over the cells whose centre lies within 16 view_range sub-units of the
+ * probe, and the feature is float(sum_k >> 8) * 2^-15 -- exact: sum_k <= 2^31.  Every agent reads the same grid (no claims).
+ * DEFINED by gridobs.grid_features_torch and gridobs.feature_episodes_torch (stock torch ops, integer after one quantisation);
+ * the kernels reproduce them bit for bit.
+ *   cs_grid_features     per decision, on the grid cs_coverage_actions or cs_belief_actions left after its call on the same state:
+ *     state_dev  float [B][state_width], in     grid_dev  int32 [B][side * side], in (READ ONLY)     feat_dev  float [B][n_agents][16], out
+ *   cs_feature_episodes  for a recorded batch: cs_label_episodes' walk (same params, same s_dev / lens_dev / outputs) that also
+ *     writes the features of the grid as every live row's step left it:
+ *     feat_dev  float [E][T][n_agents][16], out (rows t >= lens[e]: 0)     labels_dev  int64 [E][T][n_agents], out, or NULL: the
+ *     choose step is skipped altogether     grid_out_dev, prev_out_dev  as cs_label_episodes', or NULL */
+typedef struct cs_grid_params {
+    int32_t n_agents;     /* 1..8 */
+    int32_t side;         /* map_size: cells per side, 1..CS_MAX_MAP */
+    int32_t view_range;   /* sensor radius in cells, 0..CS_MAX_MAP */
+    int32_t lookahead;    /* distance of the inner ring in cells, 0..side */
+    int32_t state_width;  /* floats per state row, >= 4 n_agents */
+    int32_t reserved;     /* must be 0 (CS_E_CONFIG otherwise) */
+} cs_grid_params;
+
+/* One launch each on `stream`, one workgroup per env / per episode, no global atomics (cs_feature_episodes: LDS atomics as
+ * cs_label_episodes), no synchronisation.  CS_E_CONFIG (before any launch) for a field out of range, a non-zero `reserved`, a NULL or
+ * misaligned pointer (labels_dev, grid_out_dev and prev_out_dev may be NULL; prev_out_dev must be NULL for the coverage filter), B <
+ * 1, E < 1 or T < 1.  The message is cs_episodes_last_error()'s. */
+int cs_grid_features(const cs_grid_params *p, const float *state_dev, int B, const int32_t *grid_dev, float *feat_dev, void *stream);
+int cs_feature_episodes(const cs_label_params *p, const float *s_dev, int E, int T, const int32_t *lens_dev, float *feat_dev,
+                        int64_t *labels_dev, int32_t *grid_out_dev, int32_t *prev_out_dev, void *stream);
 
 /* ---- QMIX learner: the GRU recurrence of the agent network over T steps, forward and backward ---------------------
  * Replaces the per-transition unroll of policy/qmix.py:160-182 (get_q_values) over network/base_net.py:40-46
