@@ -19,6 +19,7 @@ from .learner import PPOLearner, PPOPolicyLoss, ValueCritic, gae, get_ppo_args  
 from .runner import Runner, get_model_idx, run_name  # noqa: F401
 from .snapshot import EnvSnapshot  # noqa: F401
 from .baseline import CoverageAgents, coverage_actions_torch  # noqa: F401
+from .local import LocalCoverageAgents, local_coverage_actions_torch  # noqa: F401
 from .sweep import SweepResult, sweep_episodes, sweep_episodes_torch, sweep_batch, swept_curve, sweep_efficiency  # noqa: F401
 from .sweep import sweep_bonus, with_sweep_bonus, collect_sweep_data  # noqa: F401
 from .motion import TargetMotion, MovingTargetEnv, move_targets_torch, make_env  # noqa: F401

@@ -153,6 +153,7 @@ __global__ __launch_bounds__(256) void k_compact_small(CompactParams p) {
 
 #include "render.h"   // k_render_episodes: episode rows -> RGB frames (cs_render_episodes)
 #include "coverage.h" // k_coverage_actions: the greedy coverage baseline (cs_coverage_actions)
+#include "local.h"    // k_local_coverage_actions: the coverage baseline on n private grids under a communication range (cs_local_coverage_actions)
 #include "sweep.h"    // k_sweep_episodes: swept-area accounting of recorded episodes (cs_sweep_episodes)
 #include "belief.h"   // k_belief_actions: the target-density filter policy for moving targets (cs_belief_actions)
 #include "plan.h"     // k_plan_actions: a receding-horizon sequence search over a base policy's grid (cs_plan_actions)
@@ -283,6 +284,39 @@ int cs_coverage_actions(const cs_coverage_params *p, const float *state_dev, int
     hipLaunchKernelGGL(k_coverage_actions, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
     if (hipGetLastError() != hipSuccess) {
         snprintf(g_eerr, sizeof(g_eerr), "cs_coverage_actions: kernel launch failed");
+        return CS_E_LAUNCH;
+    }
+    return CS_OK;
+}
+
+int cs_local_coverage_actions(const cs_local_params *p, const float *state_dev, int B, int32_t *grids_dev, int64_t *actions_dev,
+                              void *stream) {
+    const char *bad = nullptr;
+    if (!p || !state_dev || !grids_dev || !actions_dev) bad = "a NULL pointer";
+    else if (B < 1) bad = "B must be >= 1";
+    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
+    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
+    else if (p->view_range < 0 || p->view_range > CS_MAX_MAP) bad = "view_range must be 0..64";
+    else if (p->keep < 0 || p->keep > 65536) bad = "keep must be 0..65536";
+    else if (p->regrow < 1 || p->regrow > 16) bad = "regrow must be 1..16";
+    else if (p->lookahead < 0 || p->lookahead > p->side) bad = "lookahead must be 0..side";
+    else if (p->state_width < 4 * p->n_agents) bad = "state_width must be at least 4 n_agents";
+    else if (p->comm_range < -1 || p->comm_range > LOC_MAX_COMM) bad = "comm_range must be -1 (unlimited) or 0..128";
+    else if (p->reserved != 0) bad = "reserved must be 0";
+    else if ((uintptr_t)grids_dev % 4 != 0 || (uintptr_t)state_dev % 4 != 0 || (uintptr_t)actions_dev % 8 != 0)
+        bad = "a pointer is not aligned to its element size";
+    if (bad) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_local_coverage_actions: %s", bad);
+        return CS_E_CONFIG;
+    }
+    const int cells = p->side * p->side;
+    // rows are cells words apart, for every agent of every env: all of them are aligned when the base is and cells % 4 == 0
+    const LocalArgs a{CoverageArgs{state_dev, grids_dev, actions_dev, p->n_agents, p->side, p->state_width, 16 * p->view_range, p->keep,
+                                   p->regrow, 16 * p->lookahead, (cells % 4 == 0 && (uintptr_t)grids_dev % 16 == 0) ? 1 : 0},
+                      p->comm_range < 0 ? -1LL : (long long)(16 * p->comm_range) * (long long)(16 * p->comm_range)};
+    hipLaunchKernelGGL(k_local_coverage_actions, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_eerr, sizeof(g_eerr), "cs_local_coverage_actions: kernel launch failed");
         return CS_E_LAUNCH;
     }
     return CS_OK;

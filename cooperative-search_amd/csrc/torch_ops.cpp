@@ -638,6 +638,38 @@ void coverage_actions(const Tensor &state, Tensor grid, Tensor actions, int64_t 
     TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
 }
 
+// ---- coverage under a communication range (cs_local_coverage_actions): state [B, S >= 4n] float32, grids [B, n, side * side] int32
+// (in / out), actions [B, n] int64 (out); comm_range -1 = unlimited.  Integers and shapes first (nothing is dereferenced), then the tensors.
+void local_coverage_actions(const Tensor &state, Tensor grids, Tensor actions, int64_t n_agents, int64_t side, int64_t view_range,
+                            int64_t keep, int64_t regrow, int64_t lookahead, int64_t comm_range) {
+    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: local_coverage_actions: n_agents must be 1..8, got ", n_agents);
+    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: local_coverage_actions: side must be 1..", CS_MAX_MAP, ", got ", side);
+    TORCH_CHECK(view_range >= 0 && view_range <= CS_MAX_MAP, "coopsearch: local_coverage_actions: view_range must be 0..", CS_MAX_MAP,
+                ", got ", view_range);
+    TORCH_CHECK(keep >= 0 && keep <= 65536, "coopsearch: local_coverage_actions: keep must be 0..65536, got ", keep);
+    TORCH_CHECK(regrow >= 1 && regrow <= 16, "coopsearch: local_coverage_actions: regrow must be 1..16, got ", regrow);
+    TORCH_CHECK(lookahead >= 0 && lookahead <= side, "coopsearch: local_coverage_actions: lookahead must be 0..side, got ", lookahead);
+    TORCH_CHECK(comm_range >= -1 && comm_range <= 128, "coopsearch: local_coverage_actions: comm_range must be -1 (unlimited) or 0..128, got ",
+                comm_range);
+    TORCH_CHECK(state.dim() == 2 && state.size(0) >= 1 && state.size(0) <= INT32_MAX && state.size(1) >= 4 * n_agents &&
+                    state.size(1) <= INT32_MAX,
+                "coopsearch: local_coverage_actions: state must be [B, S] with B >= 1 and S >= 4 n_agents = ", 4 * n_agents);
+    const int64_t B = state.size(0), S = state.size(1);
+    TORCH_CHECK(grids.dim() == 3 && grids.size(0) == B && grids.size(1) == n_agents && grids.size(2) == side * side,
+                "coopsearch: local_coverage_actions: grids must be [", B, ", ", n_agents, ", ", side * side, "]");
+    TORCH_CHECK(actions.dim() == 2 && actions.size(0) == B && actions.size(1) == n_agents,
+                "coopsearch: local_coverage_actions: actions must be [", B, ", ", n_agents, "]");
+    TORCH_CHECK(state.is_cuda(), "coopsearch: local_coverage_actions: state must be a GPU tensor");
+    check_f32(state, "state", B * S, state);
+    check_dev(grids, "grids", at::kInt, B * n_agents * side * side, state);
+    check_dev(actions, "actions", at::kLong, B * n_agents, state);
+    const cs_local_params p{(int32_t)n_agents, (int32_t)side, (int32_t)view_range, (int32_t)keep, (int32_t)regrow, (int32_t)lookahead,
+                            (int32_t)S, (int32_t)comm_range, 0};
+    const int rc = cs_local_coverage_actions(&p, state.data_ptr<float>(), (int)B, grids.data_ptr<int32_t>(), actions.data_ptr<int64_t>(),
+                                             stream_of(state));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
 // ---- swept-area accounting (cs_sweep_episodes): states [E, T1, S >= 4n] float32, counts [E] int32, first [E, side * side],
 // new_cells and seen_cells [E, T1] int32 (out).  Integers and shapes first (nothing is dereferenced), then the tensors.
 void sweep_episodes(const Tensor &states, const Tensor &counts, Tensor first, Tensor new_cells, Tensor seen_cells, int64_t n_agents,
@@ -1201,6 +1233,8 @@ TORCH_LIBRARY(coopsearch, m) {
           "int layers, int[] colours, Tensor palette, Tensor lut, Tensor(a!) frames) -> ()", &render_episodes);
     m.def("coverage_actions(Tensor state, Tensor(a!) grid, Tensor(b!) actions, int n_agents, int side, int view_range, int keep, "
           "int regrow, int lookahead) -> ()", &coverage_actions);
+    m.def("local_coverage_actions(Tensor state, Tensor(a!) grids, Tensor(b!) actions, int n_agents, int side, int view_range, int keep, "
+          "int regrow, int lookahead, int comm_range) -> ()", &local_coverage_actions);
     m.def("belief_actions(Tensor state, Tensor(a!) grid, Tensor(b!) prev, Tensor(c!) actions, int n_agents, int side, int view_range, "
           "int keep, int lookahead, int mode, int moved, int sense16, int[] dx, int[] dy) -> ()", &belief_actions);
     m.def("plan_actions(Tensor state, Tensor grid, Tensor(a!) actions, Tensor(b!) plans, Tensor(c!) scores, int n_agents, int side, "

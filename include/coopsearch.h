@@ -43,7 +43,7 @@ extern "C" {
                               cs_motion_params and cs_move_targets, then cs_belief_params and cs_belief_actions,
                               then cs_plan_params and cs_plan_actions, then cs_forecast_params, cs_belief_forecast and cs_plan_forecast_actions,
                               then cs_label_params, cs_label_episodes and cs_bc_loss, then cs_grid_params, cs_grid_features and
-                              cs_feature_episodes
+                              cs_feature_episodes, then cs_local_params and cs_local_coverage_actions
                               (no existing export or struct changed: a version-7 caller works unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
@@ -522,6 +522,36 @@ typedef struct cs_coverage_params {
  * out of range, a NULL or misaligned pointer or B < 1.  The message is cs_episodes_last_error()'s. */
 int cs_coverage_actions(const cs_coverage_params *p, const float *state_dev, int B, int32_t *grid_dev, int64_t *actions_dev,
                         void *stream);
+
+/* ---- coverage under a limited communication range: n private grids per env, one launch per decision ---
+ * cs_coverage_actions decides from one grid per env: every agent knows at once what every team-mate has swept.  Here agent i keeps a
+ * grid of its own and hears only the agents within comm_range cells of it.  Per call: every grid regrows; agent i sweeps its own disc
+ * on its own grid (S_i); i and j are linked iff i == j, or comm_range < 0, or (X_i - X_j)^2 + (Y_i - Y_j)^2 < (16 comm_range)^2 in
+ * sub-units (strict, 64-bit: comm_range 0 links nobody); M_i = min over the linked j of S_j, cell by cell, is written back -- ONE hop
+ * per call: news travels along a chain of linked agents one hop per decision --; then the agents choose in index order as
+ * cs_coverage_actions' do, agent i on M_i less the chosen footprints of the linked agents before it.  With comm_range -1 and equal
+ * grids this IS cs_coverage_actions (every grid equals its grid); with comm_range 0 every agent is a one-agent cs_coverage_actions.
+ * DEFINED by local.local_coverage_actions_torch (stock torch ops, integer after one quantisation); the kernel reproduces grids and
+ * actions bit for bit.
+ *   state_dev    float [B][state_width]     grids_dev  int32 [B][n_agents][side * side], in / out, values 0..65536 (a cell outside
+ *                                           that range is read as the nearer bound)
+ *   actions_dev  int64 [B][n_agents], out: 0 straight, 1 = + pi / 18, 2 = - pi / 18 (the env's coding) */
+typedef struct cs_local_params {
+    int32_t n_agents;     /* 1..8 */
+    int32_t side;         /* map_size: cells per side, 1..CS_MAX_MAP */
+    int32_t view_range;   /* sensor radius in cells, 0..CS_MAX_MAP */
+    int32_t keep;         /* rint((1 - detect_prob) * 65536), 0..65536 */
+    int32_t regrow;       /* every call: G += (65536 - G) >> regrow; 1..16 */
+    int32_t lookahead;    /* distance of the look-ahead point in cells, 0..side */
+    int32_t state_width;  /* floats per state row, >= 4 n_agents */
+    int32_t comm_range;   /* communication range in whole cells, 0..128, or -1: unlimited */
+    int32_t reserved;     /* must be 0 (CS_E_CONFIG otherwise) */
+} cs_local_params;
+
+/* One launch on `stream`, one workgroup per env, no global atomics, no synchronisation.  CS_E_CONFIG (before any launch) for a field
+ * out of range, a non-zero `reserved`, a NULL or misaligned pointer or B < 1.  The message is cs_episodes_last_error()'s. */
+int cs_local_coverage_actions(const cs_local_params *p, const float *state_dev, int B, int32_t *grids_dev, int64_t *actions_dev,
+                              void *stream);
 
 /* ---- swept-area accounting of recorded episodes, one launch per episode batch ---------------
  * How much of the map a team's sensors have swept by row t of an episode, and how much of a row's sweeping lands on ground
