@@ -266,6 +266,17 @@ def torch_ops():
     return _ops
 
 
+def torch_ops_for(what):
+    """`torch_ops()` for a caller that has no other route to its kernels: whatever keeps the op layer from loading (no compiler, no
+    torch headers, a dlopen failure) becomes a CoopSearchError that starts with `what`, e.g. "the coverage kernel needs"."""
+    try:
+        return torch_ops()
+    except CoopSearchError:
+        raise
+    except Exception as exc:   # noqa: BLE001
+        raise CoopSearchError(f"{what} torch.ops.coopsearch, which is unavailable ({type(exc).__name__}: {exc})") from exc
+
+
 def _cfg(cfg):
     """The cs_config whose bytes the CPU uint8 tensor `cfg` holds (what the ops take; BatchedFlightEnv._cfg_t), in place."""
     return CsConfig.from_address(cfg.data_ptr())

@@ -89,18 +89,78 @@ def quantise(state, n_agents, side):
     return X, Y, h
 
 
-def _check_params(n, side, view_range, keep, regrow, lookahead):
+def _check_team(prefix, n, side, view_range):
     if not 1 <= n <= _lib.MAX_AGENTS or not 1 <= side <= MAX_MAP or not 0 <= view_range <= MAX_MAP:
-        raise ValueError(f"coverage: n_agents must be 1..{_lib.MAX_AGENTS}, side 1..{MAX_MAP} and view_range 0..{MAX_MAP}")
+        raise ValueError(f"{prefix}: n_agents must be 1..{_lib.MAX_AGENTS}, side 1..{MAX_MAP} and view_range 0..{MAX_MAP}")
+
+
+def _check_params(n, side, view_range, keep, regrow, lookahead):
+    _check_team("coverage", n, side, view_range)
     if not 0 <= keep <= FRESH or not 1 <= regrow <= 16 or not 0 <= lookahead <= side:
         raise ValueError("coverage: keep must be 0..65536, regrow 1..16 and lookahead 0..side")
 
 
-def _check_tensors(state, grid, n, side):
+def _check_state_grid(prefix, state, grid, n, shape, name="grid"):
+    """state float32 [B, S >= 4n] and `grid` int32 [B, *shape] on the state's device."""
     if state.dim() != 2 or state.dtype != torch.float32 or state.shape[0] < 1 or state.shape[1] < 4 * n:
-        raise ValueError(f"coverage: state must be float32 [B, S] with B >= 1 and S >= 4 n_agents = {4 * n}")
-    if grid.dtype != torch.int32 or tuple(grid.shape) != (state.shape[0], side * side) or grid.device != state.device:
-        raise ValueError(f"coverage: grid must be int32 [{state.shape[0]}, {side * side}] on the state's device")
+        raise ValueError(f"{prefix}: state must be float32 [B, S] with B >= 1 and S >= 4 n_agents = {4 * n}")
+    want = (state.shape[0], *shape)
+    if grid.dtype != torch.int32 or tuple(grid.shape) != want or grid.device != state.device:
+        raise ValueError(f"{prefix}: {name} must be int32 {list(want)} on the state's device")
+
+
+def cell_centres(side, device):
+    """int64 [side]: 16 i + 8, the centre of row (or column) i in sub-units of 1/16 cell."""
+    return 16 * torch.arange(side, dtype=torch.int64, device=device) + 8
+
+
+def disc_mask(centre, px, py, R2):
+    """Points int64 [B] or [B, N] -> bool [B, cells] or [B, N, cells], cell ix * side + iy: the cells whose centre (`centre`:
+    `cell_centres`) lies within R of the point, R2 = R^2 (<= on squared integers)."""
+    dx, dy = centre - px.unsqueeze(-1), centre - py.unsqueeze(-1)
+    return ((dx * dx).unsqueeze(-1) + (dy * dy).unsqueeze(-2) <= R2).flatten(-2)
+
+
+def swept(centre, X, Y, R2):
+    """bool [B, cells]: the cells within R of any of the agents X, Y int64 [B, n] (the sweep test)."""
+    seen = disc_mask(centre, X[:, 0], Y[:, 0], R2)
+    for i in range(1, X.shape[1]):
+        seen = seen | disc_mask(centre, X[:, i], Y[:, i], R2)
+    return seen
+
+
+def greedy_choose(M, X, Y, h, side, view_range, lookahead, adj=None):
+    """The choose stage of the coverage, belief and local policies -> (actions int64 [B, n], scores int64 [B, n, 3]).  M int64: the
+    swept grid, [B, cells] for one grid per env or [B, n, cells] for one per agent; X, Y, h: `quantise`'s.  Agents decide in index
+    order: agent i scores its three look-ahead footprints on its grid with the footprints zeroed that the agents j < i chose and i
+    heard of -- all of them, or with adj (bool [B, n, n]) those with adj[:, i, j]; the lowest action with the largest score wins."""
+    i64, dev = torch.int64, M.device
+    B, n = int(X.shape[0]), int(X.shape[1])
+    R2, centre = (16 * view_range) ** 2, cell_centres(side, dev)
+    ct, st = trig_tables()
+    offx = torch.tensor([(lookahead * 16 * v) >> 14 for v in ct], dtype=i64, device=dev)   # (Python's >> floors)
+    offy = torch.tensor([(lookahead * 16 * v) >> 14 for v in st], dtype=i64, device=dev)
+    zero = torch.zeros(B, side * side, dtype=i64, device=dev)
+    actions = torch.empty(B, n, dtype=i64, device=dev)
+    scores = torch.empty(B, n, 3, dtype=i64, device=dev)
+    claims = []
+    for i in range(n):
+        W = M if M.dim() == 2 else M[:, i]
+        for j in range(i):   # the claims agent i has heard
+            W = torch.where(claims[j] if adj is None else claims[j] & adj[:, i, j].view(B, 1), zero, W)
+        foot, score = [], []
+        for turn in (0, 1, HEADINGS - 1):
+            hp = (h[:, i] + turn) % HEADINGS
+            px = torch.clamp(X[:, i] + offx[hp], 0, 16 * side)
+            py = torch.clamp(Y[:, i] + offy[hp], 0, 16 * side)
+            foot.append(disc_mask(centre, px, py, R2))
+            score.append(torch.where(foot[-1], W, zero).sum(1))
+        best = (score[1] > score[0]).to(i64)
+        best = torch.where(score[2] > torch.maximum(score[0], score[1]), torch.full_like(best, 2), best)
+        actions[:, i] = best
+        scores[:, i] = torch.stack(score, 1)
+        claims.append(torch.where((best == 0).view(B, 1), foot[0], torch.where((best == 1).view(B, 1), foot[1], foot[2])))
+    return actions, scores
 
 
 def coverage_actions_torch(state, grid, n_agents, side, view_range, keep, regrow=8, lookahead=None, return_scores=False):
@@ -112,85 +172,70 @@ def coverage_actions_torch(state, grid, n_agents, side, view_range, keep, regrow
     n, side, view_range, keep, regrow = int(n_agents), int(side), int(view_range), int(keep), int(regrow)
     lookahead = min(view_range, side) if lookahead is None else int(lookahead)
     _check_params(n, side, view_range, keep, regrow, lookahead)
-    _check_tensors(state, grid, n, side)
-    i64, dev = torch.int64, state.device
-    B, R2 = int(state.shape[0]), (16 * view_range) ** 2
+    _check_state_grid("coverage", state, grid, n, (side * side,))
     X, Y, h = quantise(state, n, side)
-    centre = (16 * torch.arange(side, dtype=i64, device=dev) + 8).view(1, side)
-
-    def within(px, py):   # [B] points -> [B, cells], cell ix * side + iy
-        dx, dy = centre - px.view(B, 1), centre - py.view(B, 1)
-        return ((dx * dx).view(B, side, 1) + (dy * dy).view(B, 1, side) <= R2).view(B, side * side)
-
-    G = grid.to(i64).clamp(0, FRESH)   # a cell outside 0..65536 is read as the nearer bound
+    G = grid.to(torch.int64).clamp(0, FRESH)   # a cell outside 0..65536 is read as the nearer bound
     G = G + ((FRESH - G) >> regrow)
-    seen = within(X[:, 0], Y[:, 0])
-    for i in range(1, n):
-        seen = seen | within(X[:, i], Y[:, i])
-    G = torch.where(seen, (G * keep) >> 16, G)
+    G = torch.where(swept(cell_centres(side, state.device), X, Y, (16 * view_range) ** 2), (G * keep) >> 16, G)
     grid.copy_(G.to(torch.int32))
-    ct, st = trig_tables()
-    offx = torch.tensor([(lookahead * 16 * v) >> 14 for v in ct], dtype=i64, device=dev)   # (Python's >> floors)
-    offy = torch.tensor([(lookahead * 16 * v) >> 14 for v in st], dtype=i64, device=dev)
-    W = G.clone()
-    zero = torch.zeros_like(W)
-    actions = torch.empty(B, n, dtype=i64, device=dev)
-    scores = torch.empty(B, n, 3, dtype=i64, device=dev)
-    for i in range(n):
-        foot, score = [], []
-        for turn in (0, 1, HEADINGS - 1):
-            hp = (h[:, i] + turn) % HEADINGS
-            px = torch.clamp(X[:, i] + offx[hp], 0, 16 * side)
-            py = torch.clamp(Y[:, i] + offy[hp], 0, 16 * side)
-            foot.append(within(px, py))
-            score.append(torch.where(foot[-1], W, zero).sum(1))
-        best = (score[1] > score[0]).to(i64)
-        best = torch.where(score[2] > torch.maximum(score[0], score[1]), torch.full_like(best, 2), best)
-        actions[:, i] = best
-        scores[:, i] = torch.stack(score, 1)
-        chosen = torch.where((best == 0).view(B, 1), foot[0], torch.where((best == 1).view(B, 1), foot[1], foot[2]))
-        W = torch.where(chosen, zero, W)
+    actions, scores = greedy_choose(G, X, Y, h, side, view_range, lookahead)
     return (actions, scores) if return_scores else actions
 
 
-def _ops():
-    try:
-        return _lib.torch_ops()
-    except _lib.CoopSearchError:
-        raise
-    except Exception as exc:   # noqa: BLE001 -- compiler missing, torch headers missing, dlopen failure
-        raise _lib.CoopSearchError(f"the coverage kernel needs torch.ops.coopsearch, which is unavailable ({type(exc).__name__}: {exc})") from exc
-
-
-class CoverageAgents:
-    """The coverage baseline for a batch of envs.  env_or_args: a BatchedFlightEnv or an args namespace (map_size, n_agents,
-    view_range, detect_prob are read); batch / device default to the env's (device: "cuda" for a namespace).  lookahead: how far
-    ahead an agent looks, in cells (default view_range, at most map_size); regrow: the regrowth shift.  impl = "hip": the kernel, one launch per
-    `choose_action` on the current stream, no synchronisation; "torch": the definition, on the same device.
+class GridAgents:
+    """What CoverageAgents, BeliefAgents and LocalCoverageAgents share.  env_or_args: a BatchedFlightEnv or an args namespace
+    (map_size, n_agents, view_range, detect_prob are read); batch / device default to the env's (device: "cuda" for a namespace);
+    lookahead: how far ahead an agent looks, in cells (default view_range, at most map_size).  impl = "hip": the kernel of
+    csrc/<KERNEL>, one launch per `choose_action` on the current stream, no synchronisation; "torch": the definition, on the same
+    device.
 
     `policy()` is a `policy(obs, state, last, t)` callable for EpisodeCollector.generate_episodes(policy=...),
-    collector.evaluate and collector.collect_experiment_data; it resets the grid when t == 0."""
+    collector.evaluate and collector.collect_experiment_data; it resets when t == 0."""
+    KERNEL = None   # the header under csrc/ that holds the subclass's kernel
+    NEEDS = None    # what to say when the op layer cannot be loaded (_lib.torch_ops_for)
 
-    def __init__(self, env_or_args, batch=None, device=None, lookahead=None, regrow=8, impl="hip"):
-        src = env_or_args
+    def __init__(self, env_or_args, batch, device, lookahead, impl):
+        src, name = env_or_args, type(self).__name__
         if impl not in ("hip", "torch"):
-            raise ValueError("impl must be 'hip' (the kernel of csrc/coverage.h) or 'torch' (the definition)")
+            raise ValueError(f"impl must be 'hip' (the kernel of csrc/{self.KERNEL}) or 'torch' (the definition)")
         batch = getattr(src, "batch", None) if batch is None else batch
         if batch is None or int(batch) < 1:
-            raise ValueError("CoverageAgents: batch must be given (>= 1) with an args namespace")
+            raise ValueError(f"{name}: batch must be given (>= 1) with an args namespace")
         self.batch = int(batch)
         self.device = torch.device(device if device is not None else getattr(src, "device", "cuda"))
         if impl == "hip" and self.device.type != "cuda":
-            raise ValueError(f"CoverageAgents(impl='hip') runs a HIP kernel and {self.device} is not a GPU: there is no CPU "
+            raise ValueError(f"{name}(impl='hip') runs a HIP kernel and {self.device} is not a GPU: there is no CPU "
                              "fallback (impl='torch' runs the definition anywhere)")
         self.impl = impl
         self.n_agents, self.side = int(src.n_agents), int(src.map_size)
         if int(src.view_range) != src.view_range:
-            raise ValueError(f"CoverageAgents: view_range must be a whole number of cells, got {src.view_range!r}")
+            raise ValueError(f"{name}: view_range must be a whole number of cells, got {src.view_range!r}")
         self.view_range = int(src.view_range)
         self.keep = keep_of(src.detect_prob)
-        self.regrow = int(regrow)
         self.lookahead = min(self.view_range, self.side) if lookahead is None else int(lookahead)
+
+    def _launch(self, state):
+        """For impl "hip": (the op layer, a fresh actions tensor int64 [B, n]) once `state` is a [batch, S] tensor."""
+        if not torch.is_tensor(state) or state.dim() != 2 or int(state.shape[0]) != self.batch:
+            raise ValueError(f"{type(self).__name__}: state must be a [{self.batch}, S] tensor")
+        return _lib.torch_ops_for(self.NEEDS), torch.empty(self.batch, self.n_agents, dtype=torch.int64, device=self.device)
+
+    def policy(self):
+        def policy(obs, state, last, t):
+            if t == 0:
+                self.reset()
+            return self.choose_action(state)
+        return policy
+
+
+class CoverageAgents(GridAgents):
+    """The coverage baseline for a batch of envs: GridAgents' arguments, and regrow: the regrowth shift.  `.grid` is the belief
+    grid, int32 [B, side * side]; `reset()` fills it."""
+    KERNEL, NEEDS = "coverage.h", "the coverage kernel needs"
+
+    def __init__(self, env_or_args, batch=None, device=None, lookahead=None, regrow=8, impl="hip"):
+        super().__init__(env_or_args, batch, device, lookahead, impl)
+        self.regrow = int(regrow)
         _check_params(self.n_agents, self.side, self.view_range, self.keep, self.regrow, self.lookahead)
         self.grid = torch.full((self.batch, self.side * self.side), FRESH, dtype=torch.int32, device=self.device)
 
@@ -203,16 +248,6 @@ class CoverageAgents:
         if self.impl == "torch":
             return coverage_actions_torch(state, self.grid, self.n_agents, self.side, self.view_range, self.keep, self.regrow,
                                           self.lookahead)
-        if not torch.is_tensor(state) or state.dim() != 2 or int(state.shape[0]) != self.batch:
-            raise ValueError(f"CoverageAgents: state must be a [{self.batch}, S] tensor")
-        actions = torch.empty(self.batch, self.n_agents, dtype=torch.int64, device=self.device)
-        _ops().coverage_actions(state, self.grid, actions, self.n_agents, self.side, self.view_range, self.keep, self.regrow,
-                                self.lookahead)
+        ops, actions = self._launch(state)
+        ops.coverage_actions(state, self.grid, actions, self.n_agents, self.side, self.view_range, self.keep, self.regrow, self.lookahead)
         return actions
-
-    def policy(self):
-        def policy(obs, state, last, t):
-            if t == 0:
-                self.reset()
-            return self.choose_action(state)
-        return policy

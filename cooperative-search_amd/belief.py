@@ -91,17 +91,13 @@ class BeliefModel:
 
 
 def _check_params(n, side, view_range, keep, lookahead, moved):
-    if not 1 <= n <= _lib.MAX_AGENTS or not 1 <= side <= bl.MAX_MAP or not 0 <= view_range <= bl.MAX_MAP:
-        raise ValueError(f"belief: n_agents must be 1..{_lib.MAX_AGENTS}, side 1..{bl.MAX_MAP} and view_range 0..{bl.MAX_MAP}")
+    bl._check_team("belief", n, side, view_range)
     if not 0 <= keep <= FRESH or not 0 <= lookahead <= side or moved not in (0, 1):
         raise ValueError("belief: keep must be 0..65536, lookahead 0..side and moved 0 or 1")
 
 
 def _check_tensors(state, grid, prev, n, side):
-    if state.dim() != 2 or state.dtype != torch.float32 or state.shape[0] < 1 or state.shape[1] < 4 * n:
-        raise ValueError(f"belief: state must be float32 [B, S] with B >= 1 and S >= 4 n_agents = {4 * n}")
-    if grid.dtype != torch.int32 or tuple(grid.shape) != (state.shape[0], side * side) or grid.device != state.device:
-        raise ValueError(f"belief: grid must be int32 [{state.shape[0]}, {side * side}] on the state's device")
+    bl._check_state_grid("belief", state, grid, n, (side * side,))
     if prev.dtype != torch.int32 or tuple(prev.shape) != (state.shape[0], _lib.MAX_AGENTS, 2) or prev.device != state.device:
         raise ValueError(f"belief: prev must be int32 [{state.shape[0]}, {_lib.MAX_AGENTS}, 2] on the state's device")
 
@@ -154,93 +150,41 @@ def belief_actions_torch(state, grid, prev, n_agents, side, view_range, keep, mo
     if not isinstance(model, BeliefModel):
         raise TypeError("belief: model must be a BeliefModel")
     _check_tensors(state, grid, prev, n, side)
-    i64, dev = torch.int64, state.device
-    B, R2 = int(state.shape[0]), (16 * view_range) ** 2
     X, Y, h = bl.quantise(state, n, side)
-    centre = (16 * torch.arange(side, dtype=i64, device=dev) + 8).view(1, side)
-
-    def within(px, py):   # [B] points -> [B, cells], cell ix * side + iy
-        dx, dy = centre - px.view(B, 1), centre - py.view(B, 1)
-        return ((dx * dx).view(B, side, 1) + (dy * dy).view(B, 1, side) <= R2).view(B, side * side)
-
-    D = grid.to(i64).clamp(0, CAP)
+    D = grid.to(torch.int64).clamp(0, CAP)
     if moved:
         D = predict_torch(D, prev, n, side, model)
-    seen = within(X[:, 0], Y[:, 0])
-    for i in range(1, n):
-        seen = seen | within(X[:, i], Y[:, i])
-    D = torch.where(seen, (D * keep) >> 16, D)
+    D = torch.where(bl.swept(bl.cell_centres(side, state.device), X, Y, (16 * view_range) ** 2), (D * keep) >> 16, D)
     grid.copy_(D.to(torch.int32))
     prev[:, :n, 0] = X.to(torch.int32)
     prev[:, :n, 1] = Y.to(torch.int32)
-    ct, st = bl.trig_tables()
-    offx = torch.tensor([(lookahead * 16 * v) >> 14 for v in ct], dtype=i64, device=dev)   # (Python's >> floors)
-    offy = torch.tensor([(lookahead * 16 * v) >> 14 for v in st], dtype=i64, device=dev)
-    W = D.clone()
-    zero = torch.zeros_like(W)
-    actions = torch.empty(B, n, dtype=i64, device=dev)
-    scores = torch.empty(B, n, 3, dtype=i64, device=dev)
-    for i in range(n):
-        foot, score = [], []
-        for turn in (0, 1, bl.HEADINGS - 1):
-            hp = (h[:, i] + turn) % bl.HEADINGS
-            px = torch.clamp(X[:, i] + offx[hp], 0, 16 * side)
-            py = torch.clamp(Y[:, i] + offy[hp], 0, 16 * side)
-            foot.append(within(px, py))
-            score.append(torch.where(foot[-1], W, zero).sum(1))
-        best = (score[1] > score[0]).to(i64)
-        best = torch.where(score[2] > torch.maximum(score[0], score[1]), torch.full_like(best, 2), best)
-        actions[:, i] = best
-        scores[:, i] = torch.stack(score, 1)
-        chosen = torch.where((best == 0).view(B, 1), foot[0], torch.where((best == 1).view(B, 1), foot[1], foot[2]))
-        W = torch.where(chosen, zero, W)
+    actions, scores = bl.greedy_choose(D, X, Y, h, side, view_range, lookahead)
     return (actions, scores) if return_scores else actions
 
 
-def _ops():
-    try:
-        return _lib.torch_ops()
-    except _lib.CoopSearchError:
-        raise
-    except Exception as exc:   # noqa: BLE001 -- compiler missing, torch headers missing, dlopen failure
-        raise _lib.CoopSearchError(f"the belief kernel needs torch.ops.coopsearch, which is unavailable ({type(exc).__name__}: {exc})") from exc
+def targets_moved(motion, t):
+    """Did the targets of `motion` move in the step that led to the state of step t?  (MovingTargetEnv moves them at the start of
+    step u iff u % every == 0.)"""
+    return t > 0 and motion.speed > 0 and (t - 1) % motion.every == 0
 
 
-class BeliefAgents:
-    """The density-filter policy for a batch of envs.  env_or_args: a BatchedFlightEnv / MovingTargetEnv or an args namespace
-    (map_size, n_agents, view_range, detect_prob are read); motion: the `TargetMotion` the filter predicts with (default: the
-    env's `.motion`, else `TargetMotion.from_args`) -- a parameter of the policy, not read from the env at decision time; batch /
-    device default to the env's (device: "cuda" for a namespace); lookahead as CoverageAgents'.  impl = "hip": the kernel, one
-    launch per `choose_action` on the current stream, no synchronisation; "torch": the definition, on the same device.
+class BeliefAgents(bl.GridAgents):
+    """The density-filter policy for a batch of envs: baseline.GridAgents' arguments (a MovingTargetEnv serves as env), and motion:
+    the `TargetMotion` the filter predicts with (default: the env's `.motion`, else `TargetMotion.from_args`) -- a parameter of the
+    policy, not read from the env at decision time.  `.grid` is the density, int32 [B, side * side], `.prev` the stored positions,
+    int32 [B, 8, 2].
 
-    `policy()` is a `policy(obs, state, last, t)` callable for EpisodeCollector.generate_episodes(policy=...), collector.evaluate,
-    collect_experiment_data and collect_sweep_data; it resets at t == 0 and tells the filter whether the targets moved in the
-    step that led to `state`: moved = t > 0 and speed > 0 and (t - 1) % every == 0."""
+    `policy()` also serves collect_sweep_data; it resets at t == 0 and tells the filter whether the targets moved in the step that
+    led to `state`: `targets_moved(motion, t)`."""
+    KERNEL, NEEDS = "belief.h", "the belief kernel needs"
 
     def __init__(self, env_or_args, motion=None, batch=None, device=None, lookahead=None, impl="hip"):
-        src = env_or_args
-        if impl not in ("hip", "torch"):
-            raise ValueError("impl must be 'hip' (the kernel of csrc/belief.h) or 'torch' (the definition)")
-        batch = getattr(src, "batch", None) if batch is None else batch
-        if batch is None or int(batch) < 1:
-            raise ValueError("BeliefAgents: batch must be given (>= 1) with an args namespace")
-        self.batch = int(batch)
-        self.device = torch.device(device if device is not None else getattr(src, "device", "cuda"))
-        if impl == "hip" and self.device.type != "cuda":
-            raise ValueError(f"BeliefAgents(impl='hip') runs a HIP kernel and {self.device} is not a GPU: there is no CPU "
-                             "fallback (impl='torch' runs the definition anywhere)")
-        self.impl = impl
-        self.n_agents, self.side = int(src.n_agents), int(src.map_size)
-        if int(src.view_range) != src.view_range:
-            raise ValueError(f"BeliefAgents: view_range must be a whole number of cells, got {src.view_range!r}")
-        self.view_range = int(src.view_range)
-        self.keep = bl.keep_of(src.detect_prob)
-        self.lookahead = min(self.view_range, self.side) if lookahead is None else int(lookahead)
+        super().__init__(env_or_args, batch, device, lookahead, impl)
         _check_params(self.n_agents, self.side, self.view_range, self.keep, self.lookahead, 0)
         if motion is None:
-            motion = getattr(src, "motion", None)
+            motion = getattr(env_or_args, "motion", None)
             if not isinstance(motion, mo.TargetMotion):
-                motion = mo.TargetMotion.from_args(src)
+                motion = mo.TargetMotion.from_args(env_or_args)
         if not isinstance(motion, mo.TargetMotion):
             raise TypeError("BeliefAgents: motion must be a TargetMotion")
         self.motion = motion
@@ -260,18 +204,16 @@ class BeliefAgents:
         if self.impl == "torch":
             return belief_actions_torch(state, self.grid, self.prev, self.n_agents, self.side, self.view_range, self.keep, self.model,
                                         moved, self.lookahead)
-        if not torch.is_tensor(state) or state.dim() != 2 or int(state.shape[0]) != self.batch:
-            raise ValueError(f"BeliefAgents: state must be a [{self.batch}, S] tensor")
-        actions = torch.empty(self.batch, self.n_agents, dtype=torch.int64, device=self.device)
-        _ops().belief_actions(state, self.grid, self.prev, actions, self.n_agents, self.side, self.view_range, self.keep, self.lookahead,
-                              self.model.mode, moved, self.model.sense16, list(self.model.dx), list(self.model.dy))
+        ops, actions = self._launch(state)
+        ops.belief_actions(state, self.grid, self.prev, actions, self.n_agents, self.side, self.view_range, self.keep, self.lookahead,
+                           self.model.mode, moved, self.model.sense16, list(self.model.dx), list(self.model.dy))
         return actions
 
     def policy(self):
-        speed, every = self.motion.speed, self.motion.every
+        motion = self.motion
 
         def policy(obs, state, last, t):
             if t == 0:
                 self.reset()
-            return self.choose_action(state, t > 0 and speed > 0 and (t - 1) % every == 0)
+            return self.choose_action(state, targets_moved(motion, t))
         return policy

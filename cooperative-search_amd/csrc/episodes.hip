@@ -11,6 +11,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <initializer_list>
 #include <type_traits>
 
 #include "coopsearch.h"
@@ -163,6 +164,146 @@ __global__ __launch_bounds__(256) void k_compact_small(CompactParams p) {
 
 thread_local char g_eerr[160] = "";
 
+// ---- host helpers of the grid family's entry points (cs_coverage_actions .. cs_feature_episodes) -------------------------------
+// A check returns what is wrong (nullptr: nothing) and reads host integers only; `first` keeps the order in which they are listed.
+int fail(const char *name, const char *bad) {
+    snprintf(g_eerr, sizeof(g_eerr), "%s: %s", name, bad);
+    return CS_E_CONFIG;
+}
+
+int launched(const char *name) {
+    if (hipGetLastError() == hipSuccess) return CS_OK;
+    snprintf(g_eerr, sizeof(g_eerr), "%s: kernel launch failed", name);
+    return CS_E_LAUNCH;
+}
+
+const char *first(std::initializer_list<const char *> checks) {
+    for (const char *bad : checks)
+        if (bad) return bad;
+    return nullptr;
+}
+
+const char *bad_agents(int n) { return n < 1 || n > CS_MAX_AGENTS ? "n_agents must be 1..8" : nullptr; }
+
+const char *bad_team(int n, int side, int view_range) {
+    return first({bad_agents(n), side < 1 || side > CS_MAX_MAP ? "side must be 1..64" : nullptr,
+                  view_range < 0 || view_range > CS_MAX_MAP ? "view_range must be 0..64" : nullptr});
+}
+
+const char *bad_cover(int keep, int regrow, int lookahead, int side) {
+    return first({keep < 0 || keep > 65536 ? "keep must be 0..65536" : nullptr, regrow < 1 || regrow > 16 ? "regrow must be 1..16" : nullptr,
+                  lookahead < 0 || lookahead > side ? "lookahead must be 0..side" : nullptr});
+}
+
+const char *bad_plan(int depth, int stride, int discount) {
+    return first({depth < 1 || depth > PLAN_MAX_DEPTH ? "depth must be 1..5" : nullptr,
+                  stride < 1 || stride > PLAN_MAX_STRIDE ? "stride must be 1..8" : nullptr,
+                  discount < 0 || discount > 256 ? "discount must be 0..256" : nullptr});
+}
+
+// the motion model's integers (`moved` is cs_belief_actions' alone: 0 elsewhere); its steps come last in every entry point: bad_steps
+const char *bad_model(int mode, int moved, int sense16) {
+    return first({mode != CS_MOTION_WALK && mode != CS_MOTION_EVADE ? "mode must be CS_MOTION_WALK or CS_MOTION_EVADE" : nullptr,
+                  moved != 0 && moved != 1 ? "moved must be 0 or 1" : nullptr,
+                  sense16 < 0 || sense16 > 32 * CS_MAX_MAP ? "sense16 must be 0..2048" : nullptr});
+}
+
+const char *bad_steps(const int32_t *dx, const int32_t *dy) {
+    for (int k = 0; k < 16; k++)
+        if (dx[k] < -16 * CS_MAX_MAP || dx[k] > 16 * CS_MAX_MAP || dy[k] < -16 * CS_MAX_MAP || dy[k] > 16 * CS_MAX_MAP)
+            return "dx and dy must be -1024..1024";
+    return nullptr;
+}
+
+const char *bad_width(int state_width, int n) { return state_width < 4 * n ? "state_width must be at least 4 n_agents" : nullptr; }
+const char *bad_reserved(int reserved) { return reserved != 0 ? "reserved must be 0" : nullptr; }
+
+// pointers to 4-byte and to 8-byte elements (NULL, where an entry point allows it, is aligned)
+const char *misaligned(std::initializer_list<const void *> four, std::initializer_list<const void *> eight) {
+    bool bad = false;
+    for (const void *q : four) bad = bad || (uintptr_t)q % 4 != 0;
+    for (const void *q : eight) bad = bad || (uintptr_t)q % 8 != 0;
+    return bad ? "a pointer is not aligned to its element size" : nullptr;
+}
+
+int vec4_ok(int cells, const void *rows) { return (cells % 4 == 0 && (uintptr_t)rows % 16 == 0) ? 1 : 0; }
+
+// view_range and lookahead in cells; `rows` is the grid whose alignment decides the vector path (label.h: grid is NULL, rows the output)
+CoverageArgs cover_args(const float *state, int32_t *grid, int64_t *actions, int n, int side, int state_width, int view_range, int keep,
+                        int regrow, int lookahead, const void *rows) {
+    return CoverageArgs{state, grid, actions, n, side, state_width, 16 * view_range, keep, regrow, 16 * lookahead, vec4_ok(side * side, rows)};
+}
+
+BeliefArgs belief_args(const CoverageArgs &c, int mode, int sense16, const int32_t *dx, const int32_t *dy) {
+    BeliefArgs a{};   // prev NULL, moved 0
+    a.c = c;
+    a.mode = mode;
+    a.sense2 = (unsigned)sense16 * (unsigned)sense16;
+    for (int k = 0; k < 16; k++) {
+        a.dx[k] = dx[k];
+        a.dy[k] = dy[k];
+    }
+    return a;
+}
+
+// cs_label_episodes and cs_feature_episodes: one params struct, one ladder (they differ in their pointers and in `prev_text`)
+const char *bad_label(const cs_label_params *p, int E, int T, const void *prev_out, const char *prev_text,
+                      std::initializer_list<const void *> four, std::initializer_list<const void *> eight) {
+    return first({E < 1 || T < 1 ? "E and T must be >= 1" : nullptr,
+                  p->expert != LABEL_COVERAGE && p->expert != LABEL_BELIEF ? "expert must be 0 (coverage) or 1 (belief)" : nullptr,
+                  bad_team(p->n_agents, p->side, p->view_range), bad_cover(p->keep, p->regrow, p->lookahead, p->side),
+                  bad_width(p->state_width, p->n_agents), bad_model(p->mode, 0, p->sense16), p->every < 1 ? "every must be >= 1" : nullptr,
+                  p->moving != 0 && p->moving != 1 ? "moving must be 0 or 1" : nullptr, bad_reserved(p->reserved),
+                  p->expert == LABEL_COVERAGE && prev_out ? prev_text : nullptr, misaligned(four, eight), bad_steps(p->dx, p->dy)});
+}
+
+LabelArgs label_args(const cs_label_params *p, const float *s, int T, const int32_t *lens, int64_t *labels, int32_t *grid_out,
+                     int32_t *prev_out) {
+    LabelArgs a{};
+    a.b = belief_args(cover_args(s, nullptr, labels, p->n_agents, p->side, p->state_width, p->view_range, p->keep, p->regrow, p->lookahead,
+                                 grid_out),
+                      p->mode, p->sense16, p->dx, p->dy);
+    a.lens = lens;
+    a.grid_out = grid_out;
+    a.prev_out = prev_out;
+    a.T = T;
+    a.expert = p->expert;
+    a.every = p->every;
+    a.moving = p->moving;
+    a.svec = (p->state_width % 4 == 0 && (uintptr_t)s % 16 == 0) ? 1 : 0;
+    a.lvec = (uintptr_t)labels % 16 == 0 ? 1 : 0;
+    return a;
+}
+
+// cs_plan_actions (levels: the base policy's grid) and cs_plan_forecast_actions (forecast: the stack of cs_belief_forecast, staged in LDS)
+int plan_launch(const char *name, bool forecast, const cs_plan_params *p, const float *state, int B, const int32_t *levels, int64_t *actions,
+                int64_t *plans, int64_t *scores, void *stream) {
+    if (!p || !state || !levels || !actions || !plans || !scores) return fail(name, "a NULL pointer");
+    const char *bad = first({B < 1 ? "B must be >= 1" : nullptr, bad_team(p->n_agents, p->side, p->view_range),
+                             bad_plan(p->depth, p->stride, p->discount), bad_width(p->state_width, p->n_agents), bad_reserved(p->reserved),
+                             misaligned({levels, state}, {actions, plans, scores})});
+    if (bad) return fail(name, bad);
+    const int cells = p->side * p->side, level_words = (cells + 3) & ~3;
+    int seqs = 1;
+    for (int d = 0; d < p->depth; d++) seqs *= 3;
+    const PlanArgs a{state, levels, actions, plans, scores, p->n_agents, p->side, p->state_width, 16 * p->view_range,
+                     p->depth, p->stride, p->discount, (3 * seqs - 3) / 2, seqs, vec4_ok(cells, levels)};
+    if (!forecast) {
+        hipLaunchKernelGGL(k_plan_actions, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
+        return launched(name);
+    }
+    const size_t lds = fc_plan_lds_bytes(p->depth, level_words);
+    // more than 64 KB of dynamic LDS (side 64 with depth 4 or 5) is granted only to a kernel that asked for it
+    if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void *>(&k_plan_forecast_actions),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        (void)hipGetLastError();
+        snprintf(g_eerr, sizeof(g_eerr), "%s: the device does not grant %zu bytes of LDS", name, lds);
+        return CS_E_LAUNCH;
+    }
+    hipLaunchKernelGGL(k_plan_forecast_actions, dim3((unsigned)B), dim3(COV_THREADS), lds, (hipStream_t)stream, a, level_words);
+    return launched(name);
+}
+
 }  // namespace
 
 extern "C" {
@@ -229,7 +370,7 @@ int cs_render_episodes(const cs_render_params *p, const float *states_dev, const
                        int E, int R, uint8_t *frames_dev, void *stream) {
     const char *bad = nullptr;
     if (!p || !states_dev || !counts_dev || !frames_dev || !p->palette_dev || !p->lut_dev) bad = "a NULL pointer";
-    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
+    else if (bad_agents(p->n_agents)) bad = bad_agents(p->n_agents);
     else if (p->n_targets < 1 || p->n_targets > CS_MAX_TARGETS) bad = "n_targets must be 1..16";
     else if (p->state_width != 4 * p->n_agents + 3 * p->n_targets) bad = "state_width must be 4 n_agents + 3 n_targets";
     else if (p->size < 16 || p->size > 1024 || p->size % 4 != 0) bad = "size must be a multiple of 4 in 16..1024";
@@ -240,10 +381,7 @@ int cs_render_episodes(const cs_render_params *p, const float *states_dev, const
     else if ((uintptr_t)frames_dev % 4 != 0) bad = "frames_dev must be 4-byte aligned";
     else if (maps_dev && (p->side < 1 || p->side > CS_MAX_MAP || p->map_width != p->side * p->side))
         bad = "side must be 1..64 and map_width side * side";
-    if (bad) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_render_episodes: %s", bad);
-        return CS_E_CONFIG;
-    }
+    if (bad) return fail(__func__, bad);
     auto rgb = [](const uint8_t *c) { return (unsigned)c[0] | ((unsigned)c[1] << 8) | ((unsigned)c[2] << 16); };
     const RenderArgs a{states_dev, maps_dev, counts_dev, frames_dev, p->palette_dev, p->lut_dev, R, p->state_width, p->n_agents,
                        p->n_targets, p->size, maps_dev ? p->side : 0, maps_dev ? p->map_width : 0, p->rv, p->rt, p->rtr, p->tri_len,
@@ -252,411 +390,139 @@ int cs_render_episodes(const cs_render_params *p, const float *states_dev, const
     const int quads = p->size * p->size / 4;
     hipLaunchKernelGGL(k_render_episodes, dim3((quads + RENDER_THREADS - 1) / RENDER_THREADS, E), dim3(RENDER_THREADS), 0,
                        (hipStream_t)stream, a);
-    if (hipGetLastError() != hipSuccess) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_render_episodes: kernel launch failed");
-        return CS_E_LAUNCH;
-    }
-    return CS_OK;
+    return launched(__func__);
 }
 
 int cs_coverage_actions(const cs_coverage_params *p, const float *state_dev, int B, int32_t *grid_dev, int64_t *actions_dev,
                         void *stream) {
-    const char *bad = nullptr;
-    if (!p || !state_dev || !grid_dev || !actions_dev) bad = "a NULL pointer";
-    else if (B < 1) bad = "B must be >= 1";
-    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
-    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
-    else if (p->view_range < 0 || p->view_range > CS_MAX_MAP) bad = "view_range must be 0..64";
-    else if (p->keep < 0 || p->keep > 65536) bad = "keep must be 0..65536";
-    else if (p->regrow < 1 || p->regrow > 16) bad = "regrow must be 1..16";
-    else if (p->lookahead < 0 || p->lookahead > p->side) bad = "lookahead must be 0..side";
-    else if (p->state_width < 4 * p->n_agents) bad = "state_width must be at least 4 n_agents";
-    else if (p->reserved != 0) bad = "reserved must be 0";
-    else if ((uintptr_t)grid_dev % 4 != 0 || (uintptr_t)state_dev % 4 != 0 || (uintptr_t)actions_dev % 8 != 0)
-        bad = "a pointer is not aligned to its element size";
-    if (bad) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_coverage_actions: %s", bad);
-        return CS_E_CONFIG;
-    }
-    const int cells = p->side * p->side;
-    const CoverageArgs a{state_dev, grid_dev, actions_dev, p->n_agents, p->side, p->state_width, 16 * p->view_range, p->keep, p->regrow,
-                         16 * p->lookahead, (cells % 4 == 0 && (uintptr_t)grid_dev % 16 == 0) ? 1 : 0};
+    if (!p || !state_dev || !grid_dev || !actions_dev) return fail(__func__, "a NULL pointer");
+    const char *bad = first({B < 1 ? "B must be >= 1" : nullptr, bad_team(p->n_agents, p->side, p->view_range),
+                             bad_cover(p->keep, p->regrow, p->lookahead, p->side), bad_width(p->state_width, p->n_agents), bad_reserved(p->reserved),
+                             misaligned({grid_dev, state_dev}, {actions_dev})});
+    if (bad) return fail(__func__, bad);
+    const CoverageArgs a = cover_args(state_dev, grid_dev, actions_dev, p->n_agents, p->side, p->state_width, p->view_range, p->keep,
+                                      p->regrow, p->lookahead, grid_dev);
     hipLaunchKernelGGL(k_coverage_actions, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
-    if (hipGetLastError() != hipSuccess) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_coverage_actions: kernel launch failed");
-        return CS_E_LAUNCH;
-    }
-    return CS_OK;
+    return launched(__func__);
 }
 
 int cs_local_coverage_actions(const cs_local_params *p, const float *state_dev, int B, int32_t *grids_dev, int64_t *actions_dev,
                               void *stream) {
-    const char *bad = nullptr;
-    if (!p || !state_dev || !grids_dev || !actions_dev) bad = "a NULL pointer";
-    else if (B < 1) bad = "B must be >= 1";
-    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
-    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
-    else if (p->view_range < 0 || p->view_range > CS_MAX_MAP) bad = "view_range must be 0..64";
-    else if (p->keep < 0 || p->keep > 65536) bad = "keep must be 0..65536";
-    else if (p->regrow < 1 || p->regrow > 16) bad = "regrow must be 1..16";
-    else if (p->lookahead < 0 || p->lookahead > p->side) bad = "lookahead must be 0..side";
-    else if (p->state_width < 4 * p->n_agents) bad = "state_width must be at least 4 n_agents";
-    else if (p->comm_range < -1 || p->comm_range > LOC_MAX_COMM) bad = "comm_range must be -1 (unlimited) or 0..128";
-    else if (p->reserved != 0) bad = "reserved must be 0";
-    else if ((uintptr_t)grids_dev % 4 != 0 || (uintptr_t)state_dev % 4 != 0 || (uintptr_t)actions_dev % 8 != 0)
-        bad = "a pointer is not aligned to its element size";
-    if (bad) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_local_coverage_actions: %s", bad);
-        return CS_E_CONFIG;
-    }
-    const int cells = p->side * p->side;
+    if (!p || !state_dev || !grids_dev || !actions_dev) return fail(__func__, "a NULL pointer");
+    const char *bad = first({B < 1 ? "B must be >= 1" : nullptr, bad_team(p->n_agents, p->side, p->view_range),
+                             bad_cover(p->keep, p->regrow, p->lookahead, p->side), bad_width(p->state_width, p->n_agents),
+                             p->comm_range < -1 || p->comm_range > LOC_MAX_COMM ? "comm_range must be -1 (unlimited) or 0..128" : nullptr,
+                             bad_reserved(p->reserved), misaligned({grids_dev, state_dev}, {actions_dev})});
+    if (bad) return fail(__func__, bad);
     // rows are cells words apart, for every agent of every env: all of them are aligned when the base is and cells % 4 == 0
-    const LocalArgs a{CoverageArgs{state_dev, grids_dev, actions_dev, p->n_agents, p->side, p->state_width, 16 * p->view_range, p->keep,
-                                   p->regrow, 16 * p->lookahead, (cells % 4 == 0 && (uintptr_t)grids_dev % 16 == 0) ? 1 : 0},
+    const LocalArgs a{cover_args(state_dev, grids_dev, actions_dev, p->n_agents, p->side, p->state_width, p->view_range, p->keep,
+                                 p->regrow, p->lookahead, grids_dev),
                       p->comm_range < 0 ? -1LL : (long long)(16 * p->comm_range) * (long long)(16 * p->comm_range)};
     hipLaunchKernelGGL(k_local_coverage_actions, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
-    if (hipGetLastError() != hipSuccess) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_local_coverage_actions: kernel launch failed");
-        return CS_E_LAUNCH;
-    }
-    return CS_OK;
+    return launched(__func__);
 }
 
 int cs_sweep_episodes(const cs_sweep_params *p, const float *states_dev, const int32_t *counts_dev, int E, int32_t *first_dev,
                       int32_t *new_dev, int32_t *seen_dev, void *stream) {
-    const char *bad = nullptr;
-    if (!p || !states_dev || !counts_dev || !first_dev || !new_dev || !seen_dev) bad = "a NULL pointer";
-    else if (E < 1) bad = "E must be >= 1";
-    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
-    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
-    else if (p->view_range < 0 || p->view_range > CS_MAX_MAP) bad = "view_range must be 0..64";
-    else if (p->state_width < 4 * p->n_agents) bad = "state_width must be at least 4 n_agents";
-    else if (p->rows < 1) bad = "rows must be >= 1";
-    else if (p->reserved != 0) bad = "reserved must be 0";
-    else if ((uintptr_t)states_dev % 4 != 0 || (uintptr_t)counts_dev % 4 != 0 || (uintptr_t)first_dev % 4 != 0 ||
-             (uintptr_t)new_dev % 4 != 0 || (uintptr_t)seen_dev % 4 != 0)
-        bad = "a pointer is not aligned to its element size";
-    if (bad) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_sweep_episodes: %s", bad);
-        return CS_E_CONFIG;
-    }
+    if (!p || !states_dev || !counts_dev || !first_dev || !new_dev || !seen_dev) return fail(__func__, "a NULL pointer");
+    const char *bad = first({E < 1 ? "E must be >= 1" : nullptr, bad_team(p->n_agents, p->side, p->view_range),
+                             bad_width(p->state_width, p->n_agents), p->rows < 1 ? "rows must be >= 1" : nullptr,
+                             bad_reserved(p->reserved),
+                             misaligned({states_dev, counts_dev, first_dev, new_dev, seen_dev}, {})});
+    if (bad) return fail(__func__, bad);
     const SweepArgs a{states_dev, counts_dev, first_dev, new_dev, seen_dev, p->n_agents, p->side, p->state_width, p->rows, 16 * p->view_range};
     hipLaunchKernelGGL(k_sweep_episodes, dim3((unsigned)E), dim3(SWEEP_THREADS), 0, (hipStream_t)stream, a);
-    if (hipGetLastError() != hipSuccess) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_sweep_episodes: kernel launch failed");
-        return CS_E_LAUNCH;
-    }
-    return CS_OK;
+    return launched(__func__);
 }
 
 int cs_belief_actions(const cs_belief_params *p, const float *state_dev, int B, int32_t *grid_dev, int32_t *prev_dev,
                       int64_t *actions_dev, void *stream) {
-    const char *bad = nullptr;
-    if (!p || !state_dev || !grid_dev || !prev_dev || !actions_dev) bad = "a NULL pointer";
-    else if (B < 1) bad = "B must be >= 1";
-    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
-    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
-    else if (p->view_range < 0 || p->view_range > CS_MAX_MAP) bad = "view_range must be 0..64";
-    else if (p->keep < 0 || p->keep > 65536) bad = "keep must be 0..65536";
-    else if (p->lookahead < 0 || p->lookahead > p->side) bad = "lookahead must be 0..side";
-    else if (p->state_width < 4 * p->n_agents) bad = "state_width must be at least 4 n_agents";
-    else if (p->mode != CS_MOTION_WALK && p->mode != CS_MOTION_EVADE) bad = "mode must be CS_MOTION_WALK or CS_MOTION_EVADE";
-    else if (p->moved != 0 && p->moved != 1) bad = "moved must be 0 or 1";
-    else if (p->sense16 < 0 || p->sense16 > 32 * CS_MAX_MAP) bad = "sense16 must be 0..2048";
-    else if (p->reserved != 0) bad = "reserved must be 0";
-    else if ((uintptr_t)grid_dev % 4 != 0 || (uintptr_t)prev_dev % 4 != 0 || (uintptr_t)state_dev % 4 != 0 || (uintptr_t)actions_dev % 8 != 0)
-        bad = "a pointer is not aligned to its element size";
-    for (int k = 0; !bad && k < 16; k++)
-        if (p->dx[k] < -16 * CS_MAX_MAP || p->dx[k] > 16 * CS_MAX_MAP || p->dy[k] < -16 * CS_MAX_MAP || p->dy[k] > 16 * CS_MAX_MAP)
-            bad = "dx and dy must be -1024..1024";
-    if (bad) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_belief_actions: %s", bad);
-        return CS_E_CONFIG;
-    }
-    const int cells = p->side * p->side;
-    BeliefArgs a{};
-    a.c = CoverageArgs{state_dev, grid_dev, actions_dev, p->n_agents, p->side, p->state_width, 16 * p->view_range, p->keep, 16,
-                       16 * p->lookahead, (cells % 4 == 0 && (uintptr_t)grid_dev % 16 == 0) ? 1 : 0};
+    if (!p || !state_dev || !grid_dev || !prev_dev || !actions_dev) return fail(__func__, "a NULL pointer");
+    const char *bad = first({B < 1 ? "B must be >= 1" : nullptr, bad_team(p->n_agents, p->side, p->view_range),
+                             bad_cover(p->keep, 16, p->lookahead, p->side), bad_width(p->state_width, p->n_agents),
+                             bad_model(p->mode, p->moved, p->sense16), bad_reserved(p->reserved),
+                             misaligned({grid_dev, prev_dev, state_dev}, {actions_dev}), bad_steps(p->dx, p->dy)});
+    if (bad) return fail(__func__, bad);
+    BeliefArgs a = belief_args(cover_args(state_dev, grid_dev, actions_dev, p->n_agents, p->side, p->state_width, p->view_range, p->keep,
+                                          16, p->lookahead, grid_dev),
+                               p->mode, p->sense16, p->dx, p->dy);
     a.prev = prev_dev;
-    a.mode = p->mode;
     a.moved = p->moved;
-    a.sense2 = (unsigned)p->sense16 * (unsigned)p->sense16;
-    for (int k = 0; k < 16; k++) {
-        a.dx[k] = p->dx[k];
-        a.dy[k] = p->dy[k];
-    }
     hipLaunchKernelGGL(k_belief_actions, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
-    if (hipGetLastError() != hipSuccess) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_belief_actions: kernel launch failed");
-        return CS_E_LAUNCH;
-    }
-    return CS_OK;
+    return launched(__func__);
 }
 
 int cs_plan_actions(const cs_plan_params *p, const float *state_dev, int B, const int32_t *grid_dev, int64_t *actions_dev,
                     int64_t *plans_dev, int64_t *scores_dev, void *stream) {
-    const char *bad = nullptr;
-    if (!p || !state_dev || !grid_dev || !actions_dev || !plans_dev || !scores_dev) bad = "a NULL pointer";
-    else if (B < 1) bad = "B must be >= 1";
-    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
-    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
-    else if (p->view_range < 0 || p->view_range > CS_MAX_MAP) bad = "view_range must be 0..64";
-    else if (p->depth < 1 || p->depth > PLAN_MAX_DEPTH) bad = "depth must be 1..5";
-    else if (p->stride < 1 || p->stride > PLAN_MAX_STRIDE) bad = "stride must be 1..8";
-    else if (p->discount < 0 || p->discount > 256) bad = "discount must be 0..256";
-    else if (p->state_width < 4 * p->n_agents) bad = "state_width must be at least 4 n_agents";
-    else if (p->reserved != 0) bad = "reserved must be 0";
-    else if ((uintptr_t)grid_dev % 4 != 0 || (uintptr_t)state_dev % 4 != 0 || (uintptr_t)actions_dev % 8 != 0 ||
-             (uintptr_t)plans_dev % 8 != 0 || (uintptr_t)scores_dev % 8 != 0)
-        bad = "a pointer is not aligned to its element size";
-    if (bad) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_plan_actions: %s", bad);
-        return CS_E_CONFIG;
-    }
-    const int cells = p->side * p->side;
-    int seqs = 1;
-    for (int d = 0; d < p->depth; d++) seqs *= 3;
-    const PlanArgs a{state_dev, grid_dev, actions_dev, plans_dev, scores_dev, p->n_agents, p->side, p->state_width, 16 * p->view_range,
-                     p->depth, p->stride, p->discount, (3 * seqs - 3) / 2, seqs, (cells % 4 == 0 && (uintptr_t)grid_dev % 16 == 0) ? 1 : 0};
-    hipLaunchKernelGGL(k_plan_actions, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
-    if (hipGetLastError() != hipSuccess) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_plan_actions: kernel launch failed");
-        return CS_E_LAUNCH;
-    }
-    return CS_OK;
+    return plan_launch(__func__, false, p, state_dev, B, grid_dev, actions_dev, plans_dev, scores_dev, stream);
 }
 
 int cs_belief_forecast(const cs_forecast_params *p, const int32_t *grid_dev, const int32_t *pos_dev, int B, int32_t *stack_dev,
                        void *stream) {
-    const char *bad = nullptr;
-    if (!p || !grid_dev || !pos_dev || !stack_dev) bad = "a NULL pointer";
-    else if (B < 1) bad = "B must be >= 1";
-    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
-    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
-    else if (p->levels < 1 || p->levels > FC_MAX_LEVELS) bad = "levels must be 1..5";
-    else if (p->mode != CS_MOTION_WALK && p->mode != CS_MOTION_EVADE) bad = "mode must be CS_MOTION_WALK or CS_MOTION_EVADE";
-    else if (p->sense16 < 0 || p->sense16 > 32 * CS_MAX_MAP) bad = "sense16 must be 0..2048";
-    else if (p->reserved != 0) bad = "reserved must be 0";
-    else if ((uintptr_t)grid_dev % 4 != 0 || (uintptr_t)pos_dev % 4 != 0 || (uintptr_t)stack_dev % 4 != 0)
-        bad = "a pointer is not aligned to its element size";
-    for (int k = 0; !bad && k < 16; k++)
-        if (p->dx[k] < -16 * CS_MAX_MAP || p->dx[k] > 16 * CS_MAX_MAP || p->dy[k] < -16 * CS_MAX_MAP || p->dy[k] > 16 * CS_MAX_MAP)
-            bad = "dx and dy must be -1024..1024";
+    if (!p || !grid_dev || !pos_dev || !stack_dev) return fail(__func__, "a NULL pointer");
+    const char *bad = first({B < 1 ? "B must be >= 1" : nullptr, bad_team(p->n_agents, p->side, 0),
+                             p->levels < 1 || p->levels > FC_MAX_LEVELS ? "levels must be 1..5" : nullptr,
+                             bad_model(p->mode, 0, p->sense16), bad_reserved(p->reserved),
+                             misaligned({grid_dev, pos_dev, stack_dev}, {}), bad_steps(p->dx, p->dy)});
     for (int d = 0; !bad && d < FC_MAX_LEVELS; d++)
         if (p->moves[d] < 0 || p->moves[d] > PLAN_MAX_STRIDE || (d >= p->levels && p->moves[d] != 0))
             bad = "moves must be 0..8, and 0 beyond `levels`";
-    if (bad) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_belief_forecast: %s", bad);
-        return CS_E_CONFIG;
-    }
+    if (bad) return fail(__func__, bad);
     const int cells = p->side * p->side;
     ForecastArgs a{};
+    a.b = belief_args(CoverageArgs{}, p->mode, p->sense16, p->dx, p->dy);
     a.b.c.n = p->n_agents;
     a.b.c.side = p->side;
-    a.b.mode = p->mode;
-    a.b.sense2 = (unsigned)p->sense16 * (unsigned)p->sense16;
-    for (int k = 0; k < 16; k++) {
-        a.b.dx[k] = p->dx[k];
-        a.b.dy[k] = p->dy[k];
-    }
     a.grid = grid_dev;
     a.pos = pos_dev;
     a.stack = stack_dev;
     a.levels = p->levels;
     for (int d = 0; d < FC_MAX_LEVELS; d++) a.moves[d] = p->moves[d];
-    a.vec_in = (cells % 4 == 0 && (uintptr_t)grid_dev % 16 == 0) ? 1 : 0;
-    a.vec_out = (cells % 4 == 0 && (uintptr_t)stack_dev % 16 == 0) ? 1 : 0;
+    a.vec_in = vec4_ok(cells, grid_dev);
+    a.vec_out = vec4_ok(cells, stack_dev);
     hipLaunchKernelGGL(k_belief_forecast, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
-    if (hipGetLastError() != hipSuccess) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_belief_forecast: kernel launch failed");
-        return CS_E_LAUNCH;
-    }
-    return CS_OK;
+    return launched(__func__);
 }
 
 int cs_plan_forecast_actions(const cs_plan_params *p, const float *state_dev, int B, const int32_t *stack_dev, int64_t *actions_dev,
                              int64_t *plans_dev, int64_t *scores_dev, void *stream) {
-    const char *bad = nullptr;
-    if (!p || !state_dev || !stack_dev || !actions_dev || !plans_dev || !scores_dev) bad = "a NULL pointer";
-    else if (B < 1) bad = "B must be >= 1";
-    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
-    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
-    else if (p->view_range < 0 || p->view_range > CS_MAX_MAP) bad = "view_range must be 0..64";
-    else if (p->depth < 1 || p->depth > PLAN_MAX_DEPTH) bad = "depth must be 1..5";
-    else if (p->stride < 1 || p->stride > PLAN_MAX_STRIDE) bad = "stride must be 1..8";
-    else if (p->discount < 0 || p->discount > 256) bad = "discount must be 0..256";
-    else if (p->state_width < 4 * p->n_agents) bad = "state_width must be at least 4 n_agents";
-    else if (p->reserved != 0) bad = "reserved must be 0";
-    else if ((uintptr_t)stack_dev % 4 != 0 || (uintptr_t)state_dev % 4 != 0 || (uintptr_t)actions_dev % 8 != 0 ||
-             (uintptr_t)plans_dev % 8 != 0 || (uintptr_t)scores_dev % 8 != 0)
-        bad = "a pointer is not aligned to its element size";
-    if (bad) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_plan_forecast_actions: %s", bad);
-        return CS_E_CONFIG;
-    }
-    const int cells = p->side * p->side, level_words = (cells + 3) & ~3;
-    int seqs = 1;
-    for (int d = 0; d < p->depth; d++) seqs *= 3;
-    const PlanArgs a{state_dev, stack_dev, actions_dev, plans_dev, scores_dev, p->n_agents, p->side, p->state_width, 16 * p->view_range,
-                     p->depth, p->stride, p->discount, (3 * seqs - 3) / 2, seqs, (cells % 4 == 0 && (uintptr_t)stack_dev % 16 == 0) ? 1 : 0};
-    const size_t lds = fc_plan_lds_bytes(p->depth, level_words);
-    // more than 64 KB of dynamic LDS (side 64 with depth 4 or 5) is granted only to a kernel that asked for it
-    if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void *>(&k_plan_forecast_actions),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError();
-        snprintf(g_eerr, sizeof(g_eerr), "cs_plan_forecast_actions: the device does not grant %zu bytes of LDS", lds);
-        return CS_E_LAUNCH;
-    }
-    hipLaunchKernelGGL(k_plan_forecast_actions, dim3((unsigned)B), dim3(COV_THREADS), lds, (hipStream_t)stream, a, level_words);
-    if (hipGetLastError() != hipSuccess) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_plan_forecast_actions: kernel launch failed");
-        return CS_E_LAUNCH;
-    }
-    return CS_OK;
+    return plan_launch(__func__, true, p, state_dev, B, stack_dev, actions_dev, plans_dev, scores_dev, stream);
 }
 
 int cs_label_episodes(const cs_label_params *p, const float *s_dev, int E, int T, const int32_t *lens_dev, int64_t *labels_dev,
                       int32_t *grid_out_dev, int32_t *prev_out_dev, void *stream) {
-    const char *bad = nullptr;
-    if (!p || !s_dev || !lens_dev || !labels_dev) bad = "a NULL pointer";
-    else if (E < 1 || T < 1) bad = "E and T must be >= 1";
-    else if (p->expert != LABEL_COVERAGE && p->expert != LABEL_BELIEF) bad = "expert must be 0 (coverage) or 1 (belief)";
-    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
-    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
-    else if (p->view_range < 0 || p->view_range > CS_MAX_MAP) bad = "view_range must be 0..64";
-    else if (p->keep < 0 || p->keep > 65536) bad = "keep must be 0..65536";
-    else if (p->regrow < 1 || p->regrow > 16) bad = "regrow must be 1..16";
-    else if (p->lookahead < 0 || p->lookahead > p->side) bad = "lookahead must be 0..side";
-    else if (p->state_width < 4 * p->n_agents) bad = "state_width must be at least 4 n_agents";
-    else if (p->mode != CS_MOTION_WALK && p->mode != CS_MOTION_EVADE) bad = "mode must be CS_MOTION_WALK or CS_MOTION_EVADE";
-    else if (p->sense16 < 0 || p->sense16 > 32 * CS_MAX_MAP) bad = "sense16 must be 0..2048";
-    else if (p->every < 1) bad = "every must be >= 1";
-    else if (p->moving != 0 && p->moving != 1) bad = "moving must be 0 or 1";
-    else if (p->reserved != 0) bad = "reserved must be 0";
-    else if (p->expert == LABEL_COVERAGE && prev_out_dev) bad = "prev_out_dev is the belief expert's (the coverage expert keeps no positions)";
-    else if ((uintptr_t)s_dev % 4 != 0 || (uintptr_t)lens_dev % 4 != 0 || (uintptr_t)labels_dev % 8 != 0 || (uintptr_t)grid_out_dev % 4 != 0 ||
-             (uintptr_t)prev_out_dev % 4 != 0)
-        bad = "a pointer is not aligned to its element size";
-    for (int k = 0; !bad && k < 16; k++)
-        if (p->dx[k] < -16 * CS_MAX_MAP || p->dx[k] > 16 * CS_MAX_MAP || p->dy[k] < -16 * CS_MAX_MAP || p->dy[k] > 16 * CS_MAX_MAP)
-            bad = "dx and dy must be -1024..1024";
-    if (bad) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_label_episodes: %s", bad);
-        return CS_E_CONFIG;
-    }
-    const int cells = p->side * p->side;
-    LabelArgs a{};
-    a.b.c = CoverageArgs{s_dev, nullptr, labels_dev, p->n_agents, p->side, p->state_width, 16 * p->view_range, p->keep, p->regrow,
-                         16 * p->lookahead, (cells % 4 == 0 && (uintptr_t)grid_out_dev % 16 == 0) ? 1 : 0};
-    a.b.prev = nullptr;
-    a.b.mode = p->mode;
-    a.b.moved = 0;
-    a.b.sense2 = (unsigned)p->sense16 * (unsigned)p->sense16;
-    for (int k = 0; k < 16; k++) {
-        a.b.dx[k] = p->dx[k];
-        a.b.dy[k] = p->dy[k];
-    }
-    a.lens = lens_dev;
-    a.grid_out = grid_out_dev;
-    a.prev_out = prev_out_dev;
-    a.T = T;
-    a.expert = p->expert;
-    a.every = p->every;
-    a.moving = p->moving;
-    a.svec = (p->state_width % 4 == 0 && (uintptr_t)s_dev % 16 == 0) ? 1 : 0;
-    a.lvec = (uintptr_t)labels_dev % 16 == 0 ? 1 : 0;
+    if (!p || !s_dev || !lens_dev || !labels_dev) return fail(__func__, "a NULL pointer");
+    const char *bad = bad_label(p, E, T, prev_out_dev, "prev_out_dev is the belief expert's (the coverage expert keeps no positions)",
+                                {s_dev, lens_dev, grid_out_dev, prev_out_dev}, {labels_dev});
+    if (bad) return fail(__func__, bad);
+    const LabelArgs a = label_args(p, s_dev, T, lens_dev, labels_dev, grid_out_dev, prev_out_dev);
     hipLaunchKernelGGL(k_label_episodes, dim3((unsigned)E), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
-    if (hipGetLastError() != hipSuccess) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_label_episodes: kernel launch failed");
-        return CS_E_LAUNCH;
-    }
-    return CS_OK;
+    return launched(__func__);
 }
 
 int cs_grid_features(const cs_grid_params *p, const float *state_dev, int B, const int32_t *grid_dev, float *feat_dev, void *stream) {
-    const char *bad = nullptr;
-    if (!p || !state_dev || !grid_dev || !feat_dev) bad = "a NULL pointer";
-    else if (B < 1) bad = "B must be >= 1";
-    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
-    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
-    else if (p->view_range < 0 || p->view_range > CS_MAX_MAP) bad = "view_range must be 0..64";
-    else if (p->lookahead < 0 || p->lookahead > p->side) bad = "lookahead must be 0..side";
-    else if (p->state_width < 4 * p->n_agents) bad = "state_width must be at least 4 n_agents";
-    else if (p->reserved != 0) bad = "reserved must be 0";
-    else if ((uintptr_t)grid_dev % 4 != 0 || (uintptr_t)state_dev % 4 != 0 || (uintptr_t)feat_dev % 4 != 0)
-        bad = "a pointer is not aligned to its element size";
-    if (bad) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_grid_features: %s", bad);
-        return CS_E_CONFIG;
-    }
+    if (!p || !state_dev || !grid_dev || !feat_dev) return fail(__func__, "a NULL pointer");
+    const char *bad = first({B < 1 ? "B must be >= 1" : nullptr, bad_team(p->n_agents, p->side, p->view_range),
+                             bad_cover(0, 1, p->lookahead, p->side), bad_width(p->state_width, p->n_agents), bad_reserved(p->reserved),
+                             misaligned({grid_dev, state_dev, feat_dev}, {})});
+    if (bad) return fail(__func__, bad);
     const GridObsArgs a{state_dev, grid_dev, feat_dev, p->n_agents, p->side, p->state_width, 16 * p->view_range, 16 * p->lookahead};
     hipLaunchKernelGGL(k_grid_features, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
-    if (hipGetLastError() != hipSuccess) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_grid_features: kernel launch failed");
-        return CS_E_LAUNCH;
-    }
-    return CS_OK;
+    return launched(__func__);
 }
 
 int cs_feature_episodes(const cs_label_params *p, const float *s_dev, int E, int T, const int32_t *lens_dev, float *feat_dev,
                         int64_t *labels_dev, int32_t *grid_out_dev, int32_t *prev_out_dev, void *stream) {
-    const char *bad = nullptr;
-    if (!p || !s_dev || !lens_dev || !feat_dev) bad = "a NULL pointer";
-    else if (E < 1 || T < 1) bad = "E and T must be >= 1";
-    else if (p->expert != LABEL_COVERAGE && p->expert != LABEL_BELIEF) bad = "expert must be 0 (coverage) or 1 (belief)";
-    else if (p->n_agents < 1 || p->n_agents > CS_MAX_AGENTS) bad = "n_agents must be 1..8";
-    else if (p->side < 1 || p->side > CS_MAX_MAP) bad = "side must be 1..64";
-    else if (p->view_range < 0 || p->view_range > CS_MAX_MAP) bad = "view_range must be 0..64";
-    else if (p->keep < 0 || p->keep > 65536) bad = "keep must be 0..65536";
-    else if (p->regrow < 1 || p->regrow > 16) bad = "regrow must be 1..16";
-    else if (p->lookahead < 0 || p->lookahead > p->side) bad = "lookahead must be 0..side";
-    else if (p->state_width < 4 * p->n_agents) bad = "state_width must be at least 4 n_agents";
-    else if (p->mode != CS_MOTION_WALK && p->mode != CS_MOTION_EVADE) bad = "mode must be CS_MOTION_WALK or CS_MOTION_EVADE";
-    else if (p->sense16 < 0 || p->sense16 > 32 * CS_MAX_MAP) bad = "sense16 must be 0..2048";
-    else if (p->every < 1) bad = "every must be >= 1";
-    else if (p->moving != 0 && p->moving != 1) bad = "moving must be 0 or 1";
-    else if (p->reserved != 0) bad = "reserved must be 0";
-    else if (p->expert == LABEL_COVERAGE && prev_out_dev) bad = "prev_out_dev is the belief filter's (the coverage filter keeps no positions)";
-    else if ((uintptr_t)s_dev % 4 != 0 || (uintptr_t)lens_dev % 4 != 0 || (uintptr_t)feat_dev % 4 != 0 || (uintptr_t)labels_dev % 8 != 0 ||
-             (uintptr_t)grid_out_dev % 4 != 0 || (uintptr_t)prev_out_dev % 4 != 0)
-        bad = "a pointer is not aligned to its element size";
-    for (int k = 0; !bad && k < 16; k++)
-        if (p->dx[k] < -16 * CS_MAX_MAP || p->dx[k] > 16 * CS_MAX_MAP || p->dy[k] < -16 * CS_MAX_MAP || p->dy[k] > 16 * CS_MAX_MAP)
-            bad = "dx and dy must be -1024..1024";
-    if (bad) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_feature_episodes: %s", bad);
-        return CS_E_CONFIG;
-    }
-    const int cells = p->side * p->side;
+    if (!p || !s_dev || !lens_dev || !feat_dev) return fail(__func__, "a NULL pointer");
+    const char *bad = bad_label(p, E, T, prev_out_dev, "prev_out_dev is the belief filter's (the coverage filter keeps no positions)",
+                                {s_dev, lens_dev, feat_dev, grid_out_dev, prev_out_dev}, {labels_dev});
+    if (bad) return fail(__func__, bad);
     FeatArgs f{};
-    LabelArgs &a = f.l;
-    a.b.c = CoverageArgs{s_dev, nullptr, labels_dev, p->n_agents, p->side, p->state_width, 16 * p->view_range, p->keep, p->regrow,
-                         16 * p->lookahead, (cells % 4 == 0 && (uintptr_t)grid_out_dev % 16 == 0) ? 1 : 0};
-    a.b.prev = nullptr;
-    a.b.mode = p->mode;
-    a.b.moved = 0;
-    a.b.sense2 = (unsigned)p->sense16 * (unsigned)p->sense16;
-    for (int k = 0; k < 16; k++) {
-        a.b.dx[k] = p->dx[k];
-        a.b.dy[k] = p->dy[k];
-    }
-    a.lens = lens_dev;
-    a.grid_out = grid_out_dev;
-    a.prev_out = prev_out_dev;
-    a.T = T;
-    a.expert = p->expert;
-    a.every = p->every;
-    a.moving = p->moving;
-    a.svec = (p->state_width % 4 == 0 && (uintptr_t)s_dev % 16 == 0) ? 1 : 0;
-    a.lvec = (uintptr_t)labels_dev % 16 == 0 ? 1 : 0;
+    f.l = label_args(p, s_dev, T, lens_dev, labels_dev, grid_out_dev, prev_out_dev);
     f.feat = feat_dev;
     f.fvec = (uintptr_t)feat_dev % 16 == 0 ? 1 : 0;
     hipLaunchKernelGGL(k_feature_episodes, dim3((unsigned)E), dim3(COV_THREADS), 0, (hipStream_t)stream, f);
-    if (hipGetLastError() != hipSuccess) {
-        snprintf(g_eerr, sizeof(g_eerr), "cs_feature_episodes: kernel launch failed");
-        return CS_E_LAUNCH;
-    }
-    return CS_OK;
+    return launched(__func__);
 }
 
 const char *cs_episodes_last_error(void) { return g_eerr; }

@@ -608,27 +608,86 @@ void render_episodes(const Tensor &states, const c10::optional<Tensor> &maps, co
     TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
 }
 
-// ---- greedy coverage baseline (cs_coverage_actions): state [B, S >= 4n] float32, grid [B, side * side] int32 (in / out),
-// actions [B, n] int64 (out).  What the shapes and integers say is checked first (nothing is dereferenced), then the tensors.
-void coverage_actions(const Tensor &state, Tensor grid, Tensor actions, int64_t n_agents, int64_t side, int64_t view_range, int64_t keep,
-                      int64_t regrow, int64_t lookahead) {
-    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: coverage_actions: n_agents must be 1..8, got ", n_agents);
-    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: coverage_actions: side must be 1..", CS_MAX_MAP, ", got ", side);
-    TORCH_CHECK(view_range >= 0 && view_range <= CS_MAX_MAP, "coopsearch: coverage_actions: view_range must be 0..", CS_MAX_MAP, ", got ",
-                view_range);
-    TORCH_CHECK(keep >= 0 && keep <= 65536, "coopsearch: coverage_actions: keep must be 0..65536, got ", keep);
-    TORCH_CHECK(regrow >= 1 && regrow <= 16, "coopsearch: coverage_actions: regrow must be 1..16, got ", regrow);
-    TORCH_CHECK(lookahead >= 0 && lookahead <= side, "coopsearch: coverage_actions: lookahead must be 0..side, got ", lookahead);
+// ---- the grid family (coverage_actions .. feature_episodes): one set of checks.  `op` is the op's name, so that every message
+// reads "coopsearch: <op>: <param> must be ..., got <v>".  What the shapes and integers say is checked first (nothing is dereferenced),
+// then the tensors.
+void check_range(const char *op, const char *name, int64_t v, int64_t lo, int64_t hi) {
+    TORCH_CHECK(v >= lo && v <= hi, "coopsearch: ", op, ": ", name, " must be ", lo, "..", hi, ", got ", v);
+}
+
+void check_flag(const char *op, const char *name, int64_t v) {
+    TORCH_CHECK(v == 0 || v == 1, "coopsearch: ", op, ": ", name, " must be 0 or 1, got ", v);
+}
+
+void check_team(const char *op, int64_t n_agents, int64_t side, int64_t view_range) {
+    check_range(op, "n_agents", n_agents, 1, CS_MAX_AGENTS);
+    check_range(op, "side", side, 1, CS_MAX_MAP);
+    check_range(op, "view_range", view_range, 0, CS_MAX_MAP);
+}
+
+void check_lookahead(const char *op, int64_t lookahead, int64_t side) {
+    TORCH_CHECK(lookahead >= 0 && lookahead <= side, "coopsearch: ", op, ": lookahead must be 0..side, got ", lookahead);
+}
+
+// the motion model's integers (`moved` is belief_actions' alone); its steps are checked by check_steps, after the op's other integers
+void check_model(const char *op, int64_t mode, int64_t sense16, int64_t moved = 0) {
+    TORCH_CHECK(mode == CS_MOTION_WALK || mode == CS_MOTION_EVADE, "coopsearch: ", op, ": mode must be 0 (walk) or 1 (evade), got ", mode);
+    check_flag(op, "moved", moved);
+    check_range(op, "sense16", sense16, 0, 32 * CS_MAX_MAP);
+}
+
+void check_steps(const char *op, at::IntArrayRef dx, at::IntArrayRef dy) {
+    TORCH_CHECK(dx.size() == 16 && dy.size() == 16, "coopsearch: ", op, ": dx and dy must hold 16 integers each");
+    for (int k = 0; k < 16; k++)
+        TORCH_CHECK(dx[k] >= -16 * CS_MAX_MAP && dx[k] <= 16 * CS_MAX_MAP && dy[k] >= -16 * CS_MAX_MAP && dy[k] <= 16 * CS_MAX_MAP,
+                    "coopsearch: ", op, ": dx and dy must be -1024..1024, got ", dx[k], " and ", dy[k], " at ", k);
+}
+
+template <class P>
+void copy_steps(P &p, at::IntArrayRef dx, at::IntArrayRef dy) {
+    for (int k = 0; k < 16; k++) {
+        p.dx[k] = (int32_t)dx[k];
+        p.dy[k] = (int32_t)dy[k];
+    }
+}
+
+struct Rows {
+    int64_t B, S;
+};
+
+// state rows [B, S >= 4 n_agents], both within int32
+Rows check_rows(const char *op, const Tensor &state, int64_t n_agents) {
     TORCH_CHECK(state.dim() == 2 && state.size(0) >= 1 && state.size(0) <= INT32_MAX && state.size(1) >= 4 * n_agents &&
                     state.size(1) <= INT32_MAX,
-                "coopsearch: coverage_actions: state must be [B, S] with B >= 1 and S >= 4 n_agents = ", 4 * n_agents);
-    const int64_t B = state.size(0), S = state.size(1);
-    TORCH_CHECK(grid.dim() == 2 && grid.size(0) == B && grid.size(1) == side * side, "coopsearch: coverage_actions: grid must be [", B,
-                ", ", side * side, "]");
-    TORCH_CHECK(actions.dim() == 2 && actions.size(0) == B && actions.size(1) == n_agents, "coopsearch: coverage_actions: actions must be [",
-                B, ", ", n_agents, "]");
-    TORCH_CHECK(state.is_cuda(), "coopsearch: coverage_actions: state must be a GPU tensor");
-    check_f32(state, "state", B * S, state);
+                "coopsearch: ", op, ": state must be [B, S] with B >= 1 and S >= 4 n_agents = ", 4 * n_agents);
+    return {state.size(0), state.size(1)};
+}
+
+void check_shape(const char *op, const Tensor &t, const char *name, at::IntArrayRef sizes) {
+    TORCH_CHECK(t.sizes() == sizes, "coopsearch: ", op, ": ", name, " must be ", sizes);
+}
+
+// the tensor every other one is held against: float32 on a GPU
+void check_lead(const char *op, const Tensor &t, const char *name, int64_t numel) {
+    TORCH_CHECK(t.is_cuda(), "coopsearch: ", op, ": ", name, " must be a GPU tensor");
+    check_f32(t, name, numel, t);
+}
+
+bool has(const c10::optional<Tensor> &t) { return t.has_value() && t->defined(); }
+
+// ---- greedy coverage baseline (cs_coverage_actions): state [B, S >= 4n] float32, grid [B, side * side] int32 (in / out),
+// actions [B, n] int64 (out).
+void coverage_actions(const Tensor &state, Tensor grid, Tensor actions, int64_t n_agents, int64_t side, int64_t view_range, int64_t keep,
+                      int64_t regrow, int64_t lookahead) {
+    const char *op = "coverage_actions";
+    check_team(op, n_agents, side, view_range);
+    check_range(op, "keep", keep, 0, 65536);
+    check_range(op, "regrow", regrow, 1, 16);
+    check_lookahead(op, lookahead, side);
+    const auto [B, S] = check_rows(op, state, n_agents);
+    check_shape(op, grid, "grid", {B, side * side});
+    check_shape(op, actions, "actions", {B, n_agents});
+    check_lead(op, state, "state", B * S);
     check_dev(grid, "grid", at::kInt, B * side * side, state);
     check_dev(actions, "actions", at::kLong, B * n_agents, state);
     const cs_coverage_params p{(int32_t)n_agents, (int32_t)side, (int32_t)view_range, (int32_t)keep, (int32_t)regrow, (int32_t)lookahead,
@@ -639,28 +698,20 @@ void coverage_actions(const Tensor &state, Tensor grid, Tensor actions, int64_t 
 }
 
 // ---- coverage under a communication range (cs_local_coverage_actions): state [B, S >= 4n] float32, grids [B, n, side * side] int32
-// (in / out), actions [B, n] int64 (out); comm_range -1 = unlimited.  Integers and shapes first (nothing is dereferenced), then the tensors.
+// (in / out), actions [B, n] int64 (out); comm_range -1 = unlimited.
 void local_coverage_actions(const Tensor &state, Tensor grids, Tensor actions, int64_t n_agents, int64_t side, int64_t view_range,
                             int64_t keep, int64_t regrow, int64_t lookahead, int64_t comm_range) {
-    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: local_coverage_actions: n_agents must be 1..8, got ", n_agents);
-    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: local_coverage_actions: side must be 1..", CS_MAX_MAP, ", got ", side);
-    TORCH_CHECK(view_range >= 0 && view_range <= CS_MAX_MAP, "coopsearch: local_coverage_actions: view_range must be 0..", CS_MAX_MAP,
-                ", got ", view_range);
-    TORCH_CHECK(keep >= 0 && keep <= 65536, "coopsearch: local_coverage_actions: keep must be 0..65536, got ", keep);
-    TORCH_CHECK(regrow >= 1 && regrow <= 16, "coopsearch: local_coverage_actions: regrow must be 1..16, got ", regrow);
-    TORCH_CHECK(lookahead >= 0 && lookahead <= side, "coopsearch: local_coverage_actions: lookahead must be 0..side, got ", lookahead);
+    const char *op = "local_coverage_actions";
+    check_team(op, n_agents, side, view_range);
+    check_range(op, "keep", keep, 0, 65536);
+    check_range(op, "regrow", regrow, 1, 16);
+    check_lookahead(op, lookahead, side);
     TORCH_CHECK(comm_range >= -1 && comm_range <= 128, "coopsearch: local_coverage_actions: comm_range must be -1 (unlimited) or 0..128, got ",
                 comm_range);
-    TORCH_CHECK(state.dim() == 2 && state.size(0) >= 1 && state.size(0) <= INT32_MAX && state.size(1) >= 4 * n_agents &&
-                    state.size(1) <= INT32_MAX,
-                "coopsearch: local_coverage_actions: state must be [B, S] with B >= 1 and S >= 4 n_agents = ", 4 * n_agents);
-    const int64_t B = state.size(0), S = state.size(1);
-    TORCH_CHECK(grids.dim() == 3 && grids.size(0) == B && grids.size(1) == n_agents && grids.size(2) == side * side,
-                "coopsearch: local_coverage_actions: grids must be [", B, ", ", n_agents, ", ", side * side, "]");
-    TORCH_CHECK(actions.dim() == 2 && actions.size(0) == B && actions.size(1) == n_agents,
-                "coopsearch: local_coverage_actions: actions must be [", B, ", ", n_agents, "]");
-    TORCH_CHECK(state.is_cuda(), "coopsearch: local_coverage_actions: state must be a GPU tensor");
-    check_f32(state, "state", B * S, state);
+    const auto [B, S] = check_rows(op, state, n_agents);
+    check_shape(op, grids, "grids", {B, n_agents, side * side});
+    check_shape(op, actions, "actions", {B, n_agents});
+    check_lead(op, state, "state", B * S);
     check_dev(grids, "grids", at::kInt, B * n_agents * side * side, state);
     check_dev(actions, "actions", at::kLong, B * n_agents, state);
     const cs_local_params p{(int32_t)n_agents, (int32_t)side, (int32_t)view_range, (int32_t)keep, (int32_t)regrow, (int32_t)lookahead,
@@ -671,26 +722,20 @@ void local_coverage_actions(const Tensor &state, Tensor grids, Tensor actions, i
 }
 
 // ---- swept-area accounting (cs_sweep_episodes): states [E, T1, S >= 4n] float32, counts [E] int32, first [E, side * side],
-// new_cells and seen_cells [E, T1] int32 (out).  Integers and shapes first (nothing is dereferenced), then the tensors.
+// new_cells and seen_cells [E, T1] int32 (out).
 void sweep_episodes(const Tensor &states, const Tensor &counts, Tensor first, Tensor new_cells, Tensor seen_cells, int64_t n_agents,
                     int64_t side, int64_t view_range) {
-    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: sweep_episodes: n_agents must be 1..8, got ", n_agents);
-    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: sweep_episodes: side must be 1..", CS_MAX_MAP, ", got ", side);
-    TORCH_CHECK(view_range >= 0 && view_range <= CS_MAX_MAP, "coopsearch: sweep_episodes: view_range must be 0..", CS_MAX_MAP, ", got ",
-                view_range);
+    const char *op = "sweep_episodes";
+    check_team(op, n_agents, side, view_range);
     TORCH_CHECK(states.dim() == 3 && states.size(0) >= 1 && states.size(0) <= INT32_MAX && states.size(1) >= 1 &&
                     states.size(1) <= INT32_MAX && states.size(2) >= 4 * n_agents && states.size(2) <= INT32_MAX,
                 "coopsearch: sweep_episodes: states must be [E, T1, S] with E >= 1, T1 >= 1 and S >= 4 n_agents = ", 4 * n_agents);
     const int64_t E = states.size(0), T1 = states.size(1), S = states.size(2);
-    TORCH_CHECK(counts.dim() == 1 && counts.size(0) == E, "coopsearch: sweep_episodes: counts must be [", E, "]");
-    TORCH_CHECK(first.dim() == 2 && first.size(0) == E && first.size(1) == side * side, "coopsearch: sweep_episodes: first must be [", E,
-                ", ", side * side, "]");
-    TORCH_CHECK(new_cells.dim() == 2 && new_cells.size(0) == E && new_cells.size(1) == T1,
-                "coopsearch: sweep_episodes: new_cells must be [", E, ", ", T1, "]");
-    TORCH_CHECK(seen_cells.dim() == 2 && seen_cells.size(0) == E && seen_cells.size(1) == T1,
-                "coopsearch: sweep_episodes: seen_cells must be [", E, ", ", T1, "]");
-    TORCH_CHECK(states.is_cuda(), "coopsearch: sweep_episodes: states must be a GPU tensor");
-    check_f32(states, "states", E * T1 * S, states);
+    check_shape(op, counts, "counts", {E});
+    check_shape(op, first, "first", {E, side * side});
+    check_shape(op, new_cells, "new_cells", {E, T1});
+    check_shape(op, seen_cells, "seen_cells", {E, T1});
+    check_lead(op, states, "states", E * T1 * S);
     check_dev(counts, "counts", at::kInt, E, states);
     check_dev(first, "first", at::kInt, E * side * side, states);
     check_dev(new_cells, "new_cells", at::kInt, E * T1, states);
@@ -724,104 +769,79 @@ void move_targets(const Tensor &cfg, Tensor blob, int64_t mode, int64_t persist,
 }
 
 // ---- target-density filter policy (cs_belief_actions): state [B, S >= 4n] float32, grid [B, side * side] int32 and prev [B, 8, 2]
-// int32 (in / out), actions [B, n] int64 (out).  Integers and shapes first (nothing is dereferenced), then the tensors.
+// int32 (in / out), actions [B, n] int64 (out).
 void belief_actions(const Tensor &state, Tensor grid, Tensor prev, Tensor actions, int64_t n_agents, int64_t side, int64_t view_range,
                     int64_t keep, int64_t lookahead, int64_t mode, int64_t moved, int64_t sense16, at::IntArrayRef dx, at::IntArrayRef dy) {
-    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: belief_actions: n_agents must be 1..8, got ", n_agents);
-    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: belief_actions: side must be 1..", CS_MAX_MAP, ", got ", side);
-    TORCH_CHECK(view_range >= 0 && view_range <= CS_MAX_MAP, "coopsearch: belief_actions: view_range must be 0..", CS_MAX_MAP, ", got ",
-                view_range);
-    TORCH_CHECK(keep >= 0 && keep <= 65536, "coopsearch: belief_actions: keep must be 0..65536, got ", keep);
-    TORCH_CHECK(lookahead >= 0 && lookahead <= side, "coopsearch: belief_actions: lookahead must be 0..side, got ", lookahead);
-    TORCH_CHECK(mode == CS_MOTION_WALK || mode == CS_MOTION_EVADE, "coopsearch: belief_actions: mode must be 0 (walk) or 1 (evade), got ", mode);
-    TORCH_CHECK(moved == 0 || moved == 1, "coopsearch: belief_actions: moved must be 0 or 1, got ", moved);
-    TORCH_CHECK(sense16 >= 0 && sense16 <= 32 * CS_MAX_MAP, "coopsearch: belief_actions: sense16 must be 0..", 32 * CS_MAX_MAP, ", got ", sense16);
-    TORCH_CHECK(dx.size() == 16 && dy.size() == 16, "coopsearch: belief_actions: dx and dy must hold 16 integers each");
-    for (int k = 0; k < 16; k++)
-        TORCH_CHECK(dx[k] >= -16 * CS_MAX_MAP && dx[k] <= 16 * CS_MAX_MAP && dy[k] >= -16 * CS_MAX_MAP && dy[k] <= 16 * CS_MAX_MAP,
-                    "coopsearch: belief_actions: dx and dy must be -1024..1024, got ", dx[k], " and ", dy[k], " at ", k);
-    TORCH_CHECK(state.dim() == 2 && state.size(0) >= 1 && state.size(0) <= INT32_MAX && state.size(1) >= 4 * n_agents &&
-                    state.size(1) <= INT32_MAX,
-                "coopsearch: belief_actions: state must be [B, S] with B >= 1 and S >= 4 n_agents = ", 4 * n_agents);
-    const int64_t B = state.size(0), S = state.size(1);
-    TORCH_CHECK(grid.dim() == 2 && grid.size(0) == B && grid.size(1) == side * side, "coopsearch: belief_actions: grid must be [", B,
-                ", ", side * side, "]");
-    TORCH_CHECK(prev.dim() == 3 && prev.size(0) == B && prev.size(1) == CS_MAX_AGENTS && prev.size(2) == 2,
-                "coopsearch: belief_actions: prev must be [", B, ", ", CS_MAX_AGENTS, ", 2]");
-    TORCH_CHECK(actions.dim() == 2 && actions.size(0) == B && actions.size(1) == n_agents, "coopsearch: belief_actions: actions must be [",
-                B, ", ", n_agents, "]");
-    TORCH_CHECK(state.is_cuda(), "coopsearch: belief_actions: state must be a GPU tensor");
-    check_f32(state, "state", B * S, state);
+    const char *op = "belief_actions";
+    check_team(op, n_agents, side, view_range);
+    check_range(op, "keep", keep, 0, 65536);
+    check_lookahead(op, lookahead, side);
+    check_model(op, mode, sense16, moved);
+    check_steps(op, dx, dy);
+    const auto [B, S] = check_rows(op, state, n_agents);
+    check_shape(op, grid, "grid", {B, side * side});
+    check_shape(op, prev, "prev", {B, CS_MAX_AGENTS, 2});
+    check_shape(op, actions, "actions", {B, n_agents});
+    check_lead(op, state, "state", B * S);
     check_dev(grid, "grid", at::kInt, B * side * side, state);
     check_dev(prev, "prev", at::kInt, B * CS_MAX_AGENTS * 2, state);
     check_dev(actions, "actions", at::kLong, B * n_agents, state);
-    cs_belief_params p{};
-    p.n_agents = (int32_t)n_agents;
-    p.side = (int32_t)side;
-    p.view_range = (int32_t)view_range;
-    p.keep = (int32_t)keep;
-    p.lookahead = (int32_t)lookahead;
-    p.state_width = (int32_t)S;
-    p.mode = (int32_t)mode;
-    p.moved = (int32_t)moved;
-    p.sense16 = (int32_t)sense16;
-    for (int k = 0; k < 16; k++) {
-        p.dx[k] = (int32_t)dx[k];
-        p.dy[k] = (int32_t)dy[k];
-    }
+    cs_belief_params p{(int32_t)n_agents, (int32_t)side, (int32_t)view_range, (int32_t)keep, (int32_t)lookahead, (int32_t)S, (int32_t)mode,
+                       (int32_t)moved, (int32_t)sense16};   // dx, dy, reserved: 0
+    copy_steps(p, dx, dy);
     const int rc = cs_belief_actions(&p, state.data_ptr<float>(), (int)B, grid.data_ptr<int32_t>(), prev.data_ptr<int32_t>(),
                                      actions.data_ptr<int64_t>(), stream_of(state));
     TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
 }
 
-// ---- receding-horizon planner (cs_plan_actions): state [B, S >= 4n] float32, grid [B, side * side] int32 (in), actions, plans and
-// scores [B, n] int64 (out).  Integers and shapes first (nothing is dereferenced), then the tensors.
-void plan_actions(const Tensor &state, const Tensor &grid, Tensor actions, Tensor plans, Tensor scores, int64_t n_agents, int64_t side,
-                  int64_t view_range, int64_t depth, int64_t stride, int64_t discount) {
-    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: plan_actions: n_agents must be 1..8, got ", n_agents);
-    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: plan_actions: side must be 1..", CS_MAX_MAP, ", got ", side);
-    TORCH_CHECK(view_range >= 0 && view_range <= CS_MAX_MAP, "coopsearch: plan_actions: view_range must be 0..", CS_MAX_MAP, ", got ",
-                view_range);
-    TORCH_CHECK(depth >= 1 && depth <= 5, "coopsearch: plan_actions: depth must be 1..5, got ", depth);
-    TORCH_CHECK(stride >= 1 && stride <= 8, "coopsearch: plan_actions: stride must be 1..8, got ", stride);
-    TORCH_CHECK(discount >= 0 && discount <= 256, "coopsearch: plan_actions: discount must be 0..256, got ", discount);
-    TORCH_CHECK(state.dim() == 2 && state.size(0) >= 1 && state.size(0) <= INT32_MAX && state.size(1) >= 4 * n_agents &&
-                    state.size(1) <= INT32_MAX,
-                "coopsearch: plan_actions: state must be [B, S] with B >= 1 and S >= 4 n_agents = ", 4 * n_agents);
-    const int64_t B = state.size(0), S = state.size(1);
-    TORCH_CHECK(grid.dim() == 2 && grid.size(0) == B && grid.size(1) == side * side, "coopsearch: plan_actions: grid must be [", B, ", ",
-                side * side, "]");
-    TORCH_CHECK(actions.dim() == 2 && actions.size(0) == B && actions.size(1) == n_agents, "coopsearch: plan_actions: actions must be [",
-                B, ", ", n_agents, "]");
-    TORCH_CHECK(plans.dim() == 2 && plans.size(0) == B && plans.size(1) == n_agents, "coopsearch: plan_actions: plans must be [", B, ", ",
-                n_agents, "]");
-    TORCH_CHECK(scores.dim() == 2 && scores.size(0) == B && scores.size(1) == n_agents, "coopsearch: plan_actions: scores must be [", B,
-                ", ", n_agents, "]");
-    TORCH_CHECK(state.is_cuda(), "coopsearch: plan_actions: state must be a GPU tensor");
-    check_f32(state, "state", B * S, state);
-    check_dev(grid, "grid", at::kInt, B * side * side, state);
+// ---- receding-horizon planner: state [B, S >= 4n] float32, actions, plans and scores [B, n] int64 (out), and what the segments are
+// scored on (in): grid [B, side * side] int32 for cs_plan_actions, stack [B, depth, side * side] int32 for cs_plan_forecast_actions.
+void plan_on(const char *op, bool forecast, const Tensor &state, const Tensor &levels, Tensor &actions, Tensor &plans, Tensor &scores,
+             int64_t n_agents, int64_t side, int64_t view_range, int64_t depth, int64_t stride, int64_t discount) {
+    const char *name = forecast ? "stack" : "grid";
+    check_team(op, n_agents, side, view_range);
+    check_range(op, "depth", depth, 1, 5);
+    check_range(op, "stride", stride, 1, 8);
+    check_range(op, "discount", discount, 0, 256);
+    const auto [B, S] = check_rows(op, state, n_agents);
+    if (forecast)
+        check_shape(op, levels, name, {B, depth, side * side});
+    else
+        check_shape(op, levels, name, {B, side * side});
+    check_shape(op, actions, "actions", {B, n_agents});
+    check_shape(op, plans, "plans", {B, n_agents});
+    check_shape(op, scores, "scores", {B, n_agents});
+    check_lead(op, state, "state", B * S);
+    check_dev(levels, name, at::kInt, B * (forecast ? depth : 1) * side * side, state);
     check_dev(actions, "actions", at::kLong, B * n_agents, state);
     check_dev(plans, "plans", at::kLong, B * n_agents, state);
     check_dev(scores, "scores", at::kLong, B * n_agents, state);
     const cs_plan_params p{(int32_t)n_agents, (int32_t)side, (int32_t)view_range, (int32_t)depth, (int32_t)stride, (int32_t)discount,
                            (int32_t)S, 0};
-    const int rc = cs_plan_actions(&p, state.data_ptr<float>(), (int)B, grid.data_ptr<int32_t>(), actions.data_ptr<int64_t>(),
-                                   plans.data_ptr<int64_t>(), scores.data_ptr<int64_t>(), stream_of(state));
+    const int rc = (forecast ? cs_plan_forecast_actions : cs_plan_actions)(&p, state.data_ptr<float>(), (int)B, levels.data_ptr<int32_t>(),
+                                                                           actions.data_ptr<int64_t>(), plans.data_ptr<int64_t>(),
+                                                                           scores.data_ptr<int64_t>(), stream_of(state));
     TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
 }
 
+void plan_actions(const Tensor &state, const Tensor &grid, Tensor actions, Tensor plans, Tensor scores, int64_t n_agents, int64_t side,
+                  int64_t view_range, int64_t depth, int64_t stride, int64_t discount) {
+    plan_on("plan_actions", false, state, grid, actions, plans, scores, n_agents, side, view_range, depth, stride, discount);
+}
+
+void plan_forecast_actions(const Tensor &state, const Tensor &stack, Tensor actions, Tensor plans, Tensor scores, int64_t n_agents,
+                           int64_t side, int64_t view_range, int64_t depth, int64_t stride, int64_t discount) {
+    plan_on("plan_forecast_actions", true, state, stack, actions, plans, scores, n_agents, side, view_range, depth, stride, discount);
+}
+
 // ---- the density along the planning horizon (cs_belief_forecast): grid [B, side * side] int32 (in), pos [B, 8, 2] int32 (in),
-// stack [B, L, side * side] int32 (out), L = moves.size().  Integers and shapes first (nothing is dereferenced), then the tensors.
+// stack [B, L, side * side] int32 (out), L = moves.size().
 void belief_forecast(const Tensor &grid, const Tensor &pos, Tensor stack, int64_t n_agents, int64_t side, int64_t mode, int64_t sense16,
                      at::IntArrayRef dx, at::IntArrayRef dy, at::IntArrayRef moves) {
-    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: belief_forecast: n_agents must be 1..8, got ", n_agents);
-    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: belief_forecast: side must be 1..", CS_MAX_MAP, ", got ", side);
-    TORCH_CHECK(mode == CS_MOTION_WALK || mode == CS_MOTION_EVADE, "coopsearch: belief_forecast: mode must be 0 (walk) or 1 (evade), got ", mode);
-    TORCH_CHECK(sense16 >= 0 && sense16 <= 32 * CS_MAX_MAP, "coopsearch: belief_forecast: sense16 must be 0..", 32 * CS_MAX_MAP, ", got ", sense16);
-    TORCH_CHECK(dx.size() == 16 && dy.size() == 16, "coopsearch: belief_forecast: dx and dy must hold 16 integers each");
-    for (int k = 0; k < 16; k++)
-        TORCH_CHECK(dx[k] >= -16 * CS_MAX_MAP && dx[k] <= 16 * CS_MAX_MAP && dy[k] >= -16 * CS_MAX_MAP && dy[k] <= 16 * CS_MAX_MAP,
-                    "coopsearch: belief_forecast: dx and dy must be -1024..1024, got ", dx[k], " and ", dy[k], " at ", k);
+    const char *op = "belief_forecast";
+    check_team(op, n_agents, side, 0);
+    check_model(op, mode, sense16);
+    check_steps(op, dx, dy);
     TORCH_CHECK(moves.size() >= 1 && moves.size() <= 5, "coopsearch: belief_forecast: moves must hold 1..5 integers, got ", moves.size());
     const int64_t L = (int64_t)moves.size();
     for (int64_t d = 0; d < L; d++)
@@ -829,62 +849,16 @@ void belief_forecast(const Tensor &grid, const Tensor &pos, Tensor stack, int64_
     TORCH_CHECK(grid.dim() == 2 && grid.size(0) >= 1 && grid.size(0) <= INT32_MAX && grid.size(1) == side * side,
                 "coopsearch: belief_forecast: grid must be [B, ", side * side, "] with B >= 1");
     const int64_t B = grid.size(0);
-    TORCH_CHECK(pos.dim() == 3 && pos.size(0) == B && pos.size(1) == CS_MAX_AGENTS && pos.size(2) == 2,
-                "coopsearch: belief_forecast: pos must be [", B, ", ", CS_MAX_AGENTS, ", 2]");
-    TORCH_CHECK(stack.dim() == 3 && stack.size(0) == B && stack.size(1) == L && stack.size(2) == side * side,
-                "coopsearch: belief_forecast: stack must be [", B, ", ", L, ", ", side * side, "]");
+    check_shape(op, pos, "pos", {B, CS_MAX_AGENTS, 2});
+    check_shape(op, stack, "stack", {B, L, side * side});
     TORCH_CHECK(grid.is_cuda(), "coopsearch: belief_forecast: grid must be a GPU tensor");
     check_dev(grid, "grid", at::kInt, B * side * side, grid);
     check_dev(pos, "pos", at::kInt, B * CS_MAX_AGENTS * 2, grid);
     check_dev(stack, "stack", at::kInt, B * L * side * side, grid);
-    cs_forecast_params p{};
-    p.n_agents = (int32_t)n_agents;
-    p.side = (int32_t)side;
-    p.levels = (int32_t)L;
-    p.mode = (int32_t)mode;
-    p.sense16 = (int32_t)sense16;
-    for (int k = 0; k < 16; k++) {
-        p.dx[k] = (int32_t)dx[k];
-        p.dy[k] = (int32_t)dy[k];
-    }
+    cs_forecast_params p{(int32_t)n_agents, (int32_t)side, (int32_t)L, (int32_t)mode, (int32_t)sense16};   // dx, dy, moves, reserved: 0
+    copy_steps(p, dx, dy);
     for (int64_t d = 0; d < L; d++) p.moves[d] = (int32_t)moves[d];
     const int rc = cs_belief_forecast(&p, grid.data_ptr<int32_t>(), pos.data_ptr<int32_t>(), (int)B, stack.data_ptr<int32_t>(), stream_of(grid));
-    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
-}
-
-// ---- the planner scored on the forecast (cs_plan_forecast_actions): plan_actions with stack [B, depth, side * side] int32 (in) in
-// the grid's place.  Integers and shapes first (nothing is dereferenced), then the tensors.
-void plan_forecast_actions(const Tensor &state, const Tensor &stack, Tensor actions, Tensor plans, Tensor scores, int64_t n_agents,
-                           int64_t side, int64_t view_range, int64_t depth, int64_t stride, int64_t discount) {
-    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: plan_forecast_actions: n_agents must be 1..8, got ", n_agents);
-    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: plan_forecast_actions: side must be 1..", CS_MAX_MAP, ", got ", side);
-    TORCH_CHECK(view_range >= 0 && view_range <= CS_MAX_MAP, "coopsearch: plan_forecast_actions: view_range must be 0..", CS_MAX_MAP,
-                ", got ", view_range);
-    TORCH_CHECK(depth >= 1 && depth <= 5, "coopsearch: plan_forecast_actions: depth must be 1..5, got ", depth);
-    TORCH_CHECK(stride >= 1 && stride <= 8, "coopsearch: plan_forecast_actions: stride must be 1..8, got ", stride);
-    TORCH_CHECK(discount >= 0 && discount <= 256, "coopsearch: plan_forecast_actions: discount must be 0..256, got ", discount);
-    TORCH_CHECK(state.dim() == 2 && state.size(0) >= 1 && state.size(0) <= INT32_MAX && state.size(1) >= 4 * n_agents &&
-                    state.size(1) <= INT32_MAX,
-                "coopsearch: plan_forecast_actions: state must be [B, S] with B >= 1 and S >= 4 n_agents = ", 4 * n_agents);
-    const int64_t B = state.size(0), S = state.size(1);
-    TORCH_CHECK(stack.dim() == 3 && stack.size(0) == B && stack.size(1) == depth && stack.size(2) == side * side,
-                "coopsearch: plan_forecast_actions: stack must be [", B, ", ", depth, ", ", side * side, "]");
-    TORCH_CHECK(actions.dim() == 2 && actions.size(0) == B && actions.size(1) == n_agents,
-                "coopsearch: plan_forecast_actions: actions must be [", B, ", ", n_agents, "]");
-    TORCH_CHECK(plans.dim() == 2 && plans.size(0) == B && plans.size(1) == n_agents, "coopsearch: plan_forecast_actions: plans must be [", B,
-                ", ", n_agents, "]");
-    TORCH_CHECK(scores.dim() == 2 && scores.size(0) == B && scores.size(1) == n_agents, "coopsearch: plan_forecast_actions: scores must be [",
-                B, ", ", n_agents, "]");
-    TORCH_CHECK(state.is_cuda(), "coopsearch: plan_forecast_actions: state must be a GPU tensor");
-    check_f32(state, "state", B * S, state);
-    check_dev(stack, "stack", at::kInt, B * depth * side * side, state);
-    check_dev(actions, "actions", at::kLong, B * n_agents, state);
-    check_dev(plans, "plans", at::kLong, B * n_agents, state);
-    check_dev(scores, "scores", at::kLong, B * n_agents, state);
-    const cs_plan_params p{(int32_t)n_agents, (int32_t)side, (int32_t)view_range, (int32_t)depth, (int32_t)stride, (int32_t)discount,
-                           (int32_t)S, 0};
-    const int rc = cs_plan_forecast_actions(&p, state.data_ptr<float>(), (int)B, stack.data_ptr<int32_t>(), actions.data_ptr<int64_t>(),
-                                            plans.data_ptr<int64_t>(), scores.data_ptr<int64_t>(), stream_of(state));
     TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
 }
 
@@ -1015,91 +989,69 @@ void bc_loss(const Tensor &logits, const Tensor &avail, const Tensor &labels, co
     TORCH_CHECK(rc == CS_OK, cs_learn_last_error());
 }
 
-// ---- an expert relabels recorded episodes (cs_label_episodes): s [E, T, S >= 4n] float32 and lens [E] int32 (in), labels [E, T, n]
-// int64, grid_out [E, side * side] int32 and prev_out [E, 8, 2] int32 (out; the last two optional).  Integers and shapes first (nothing
-// is dereferenced), then the tensors.
-void label_episodes(const Tensor &s, const Tensor &lens, Tensor labels, c10::optional<Tensor> grid_out, c10::optional<Tensor> prev_out,
-                    int64_t expert, int64_t n_agents, int64_t side, int64_t view_range, int64_t keep, int64_t regrow, int64_t lookahead,
-                    int64_t mode, int64_t sense16, int64_t every, int64_t moving, at::IntArrayRef dx, at::IntArrayRef dy) {
-    auto has = [](const c10::optional<Tensor> &t) { return t.has_value() && t->defined(); };
-    TORCH_CHECK(expert == 0 || expert == 1, "coopsearch: label_episodes: expert must be 0 (coverage) or 1 (belief), got ", expert);
-    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: label_episodes: n_agents must be 1..8, got ", n_agents);
-    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: label_episodes: side must be 1..", CS_MAX_MAP, ", got ", side);
-    TORCH_CHECK(view_range >= 0 && view_range <= CS_MAX_MAP, "coopsearch: label_episodes: view_range must be 0..", CS_MAX_MAP, ", got ",
-                view_range);
-    TORCH_CHECK(keep >= 0 && keep <= 65536, "coopsearch: label_episodes: keep must be 0..65536, got ", keep);
-    TORCH_CHECK(regrow >= 1 && regrow <= 16, "coopsearch: label_episodes: regrow must be 1..16, got ", regrow);
-    TORCH_CHECK(lookahead >= 0 && lookahead <= side, "coopsearch: label_episodes: lookahead must be 0..side, got ", lookahead);
-    TORCH_CHECK(mode == CS_MOTION_WALK || mode == CS_MOTION_EVADE, "coopsearch: label_episodes: mode must be 0 (walk) or 1 (evade), got ", mode);
-    TORCH_CHECK(sense16 >= 0 && sense16 <= 32 * CS_MAX_MAP, "coopsearch: label_episodes: sense16 must be 0..", 32 * CS_MAX_MAP, ", got ", sense16);
-    TORCH_CHECK(every >= 1 && every <= INT32_MAX, "coopsearch: label_episodes: every must be >= 1, got ", every);
-    TORCH_CHECK(moving == 0 || moving == 1, "coopsearch: label_episodes: moving must be 0 or 1, got ", moving);
-    TORCH_CHECK(dx.size() == 16 && dy.size() == 16, "coopsearch: label_episodes: dx and dy must hold 16 integers each");
-    for (int k = 0; k < 16; k++)
-        TORCH_CHECK(dx[k] >= -16 * CS_MAX_MAP && dx[k] <= 16 * CS_MAX_MAP && dy[k] >= -16 * CS_MAX_MAP && dy[k] <= 16 * CS_MAX_MAP,
-                    "coopsearch: label_episodes: dx and dy must be -1024..1024, got ", dx[k], " and ", dy[k], " at ", k);
+// ---- an expert's filter over recorded episodes: s [E, T, S >= 4n] float32 and lens [E] int32 (in); labels [E, T, n] int64, grid_out
+// [E, side * side] int32 and prev_out [E, 8, 2] int32 (out).  cs_label_episodes (feat absent): labels is required, the last two are
+// optional.  cs_feature_episodes (feat [E, T, n, 16] float32, out): labels is optional too.
+void label_on(const char *op, const char *prev_text, const Tensor &s, const Tensor &lens, const c10::optional<Tensor> &feat,
+              const c10::optional<Tensor> &labels, const c10::optional<Tensor> &grid_out, const c10::optional<Tensor> &prev_out,
+              int64_t expert, int64_t n_agents, int64_t side, int64_t view_range, int64_t keep, int64_t regrow, int64_t lookahead, int64_t mode,
+              int64_t sense16, int64_t every, int64_t moving, at::IntArrayRef dx, at::IntArrayRef dy) {
+    TORCH_CHECK(expert == 0 || expert == 1, "coopsearch: ", op, ": expert must be 0 (coverage) or 1 (belief), got ", expert);
+    check_team(op, n_agents, side, view_range);
+    check_range(op, "keep", keep, 0, 65536);
+    check_range(op, "regrow", regrow, 1, 16);
+    check_lookahead(op, lookahead, side);
+    check_model(op, mode, sense16);
+    TORCH_CHECK(every >= 1 && every <= INT32_MAX, "coopsearch: ", op, ": every must be >= 1, got ", every);
+    check_flag(op, "moving", moving);
+    check_steps(op, dx, dy);
     TORCH_CHECK(s.dim() == 3 && s.size(0) >= 1 && s.size(0) <= INT32_MAX && s.size(1) >= 1 && s.size(1) <= INT32_MAX &&
                     s.size(2) >= 4 * n_agents && s.size(2) <= INT32_MAX,
-                "coopsearch: label_episodes: s must be [E, T, S] with E >= 1, T >= 1 and S >= 4 n_agents = ", 4 * n_agents);
+                "coopsearch: ", op, ": s must be [E, T, S] with E >= 1, T >= 1 and S >= 4 n_agents = ", 4 * n_agents);
     const int64_t E = s.size(0), T = s.size(1), S = s.size(2);
-    TORCH_CHECK(lens.dim() == 1 && lens.size(0) == E, "coopsearch: label_episodes: lens must be [", E, "]");
-    TORCH_CHECK(labels.dim() == 3 && labels.size(0) == E && labels.size(1) == T && labels.size(2) == n_agents,
-                "coopsearch: label_episodes: labels must be [", E, ", ", T, ", ", n_agents, "]");
-    if (has(grid_out))
-        TORCH_CHECK(grid_out->dim() == 2 && grid_out->size(0) == E && grid_out->size(1) == side * side,
-                    "coopsearch: label_episodes: grid_out must be [", E, ", ", side * side, "]");
+    check_shape(op, lens, "lens", {E});
+    if (has(feat)) check_shape(op, *feat, "feat", {E, T, n_agents, 16});
+    if (has(labels)) check_shape(op, *labels, "labels", {E, T, n_agents});
+    if (has(grid_out)) check_shape(op, *grid_out, "grid_out", {E, side * side});
     if (has(prev_out)) {
-        TORCH_CHECK(expert == 1, "coopsearch: label_episodes: prev_out is the belief expert's (the coverage expert keeps no positions)");
-        TORCH_CHECK(prev_out->dim() == 3 && prev_out->size(0) == E && prev_out->size(1) == CS_MAX_AGENTS && prev_out->size(2) == 2,
-                    "coopsearch: label_episodes: prev_out must be [", E, ", ", CS_MAX_AGENTS, ", 2]");
+        TORCH_CHECK(expert == 1, "coopsearch: ", op, ": ", prev_text);
+        check_shape(op, *prev_out, "prev_out", {E, CS_MAX_AGENTS, 2});
     }
-    TORCH_CHECK(s.is_cuda(), "coopsearch: label_episodes: s must be a GPU tensor");
-    check_f32(s, "s", E * T * S, s);
+    check_lead(op, s, "s", E * T * S);
     check_dev(lens, "lens", at::kInt, E, s);
-    check_dev(labels, "labels", at::kLong, E * T * n_agents, s);
+    if (has(feat)) check_f32(*feat, "feat", E * T * n_agents * 16, s);
+    if (has(labels)) check_dev(*labels, "labels", at::kLong, E * T * n_agents, s);
     if (has(grid_out)) check_dev(*grid_out, "grid_out", at::kInt, E * side * side, s);
     if (has(prev_out)) check_dev(*prev_out, "prev_out", at::kInt, E * CS_MAX_AGENTS * 2, s);
-    cs_label_params p{};
-    p.expert = (int32_t)expert;
-    p.n_agents = (int32_t)n_agents;
-    p.side = (int32_t)side;
-    p.view_range = (int32_t)view_range;
-    p.keep = (int32_t)keep;
-    p.regrow = (int32_t)regrow;
-    p.lookahead = (int32_t)lookahead;
-    p.state_width = (int32_t)S;
-    p.mode = (int32_t)mode;
-    p.sense16 = (int32_t)sense16;
-    p.every = (int32_t)every;
-    p.moving = (int32_t)moving;
-    for (int k = 0; k < 16; k++) {
-        p.dx[k] = (int32_t)dx[k];
-        p.dy[k] = (int32_t)dy[k];
-    }
-    const int rc = cs_label_episodes(&p, s.data_ptr<float>(), (int)E, (int)T, lens.data_ptr<int32_t>(), labels.data_ptr<int64_t>(),
-                                     opt_ptr<int32_t>(grid_out), opt_ptr<int32_t>(prev_out), stream_of(s));
+    cs_label_params p{(int32_t)expert, (int32_t)n_agents, (int32_t)side, (int32_t)view_range, (int32_t)keep, (int32_t)regrow,
+                      (int32_t)lookahead, (int32_t)S, (int32_t)mode, (int32_t)sense16, (int32_t)every, (int32_t)moving};   // dx, dy, reserved: 0
+    copy_steps(p, dx, dy);
+    const int rc = has(feat) ? cs_feature_episodes(&p, s.data_ptr<float>(), (int)E, (int)T, lens.data_ptr<int32_t>(), feat->data_ptr<float>(),
+                                                   opt_ptr<int64_t>(labels), opt_ptr<int32_t>(grid_out), opt_ptr<int32_t>(prev_out),
+                                                   stream_of(s))
+                             : cs_label_episodes(&p, s.data_ptr<float>(), (int)E, (int)T, lens.data_ptr<int32_t>(), opt_ptr<int64_t>(labels),
+                                                 opt_ptr<int32_t>(grid_out), opt_ptr<int32_t>(prev_out), stream_of(s));
     TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
 }
 
+void label_episodes(const Tensor &s, const Tensor &lens, Tensor labels, c10::optional<Tensor> grid_out, c10::optional<Tensor> prev_out,
+                    int64_t expert, int64_t n_agents, int64_t side, int64_t view_range, int64_t keep, int64_t regrow, int64_t lookahead,
+                    int64_t mode, int64_t sense16, int64_t every, int64_t moving, at::IntArrayRef dx, at::IntArrayRef dy) {
+    label_on("label_episodes", "prev_out is the belief expert's (the coverage expert keeps no positions)", s, lens, c10::nullopt, labels,
+             grid_out, prev_out, expert, n_agents, side, view_range, keep, regrow, lookahead, mode, sense16, every, moving, dx, dy);
+}
+
 // ---- grid observations of one decision (cs_grid_features): state [B, S >= 4n] float32 and grid [B, side * side] int32 (in, read
-// only), feat [B, n, 16] float32 (out).  Integers and shapes first (nothing is dereferenced), then the tensors.
+// only), feat [B, n, 16] float32 (out).
 void grid_features(const Tensor &state, const Tensor &grid, Tensor feat, int64_t n_agents, int64_t side, int64_t view_range,
                    int64_t lookahead) {
-    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: grid_features: n_agents must be 1..8, got ", n_agents);
-    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: grid_features: side must be 1..", CS_MAX_MAP, ", got ", side);
-    TORCH_CHECK(view_range >= 0 && view_range <= CS_MAX_MAP, "coopsearch: grid_features: view_range must be 0..", CS_MAX_MAP, ", got ",
-                view_range);
-    TORCH_CHECK(lookahead >= 0 && lookahead <= side, "coopsearch: grid_features: lookahead must be 0..side, got ", lookahead);
-    TORCH_CHECK(state.dim() == 2 && state.size(0) >= 1 && state.size(0) <= INT32_MAX && state.size(1) >= 4 * n_agents &&
-                    state.size(1) <= INT32_MAX,
-                "coopsearch: grid_features: state must be [B, S] with B >= 1 and S >= 4 n_agents = ", 4 * n_agents);
-    const int64_t B = state.size(0), S = state.size(1);
-    TORCH_CHECK(grid.dim() == 2 && grid.size(0) == B && grid.size(1) == side * side, "coopsearch: grid_features: grid must be [", B, ", ",
-                side * side, "]");
-    TORCH_CHECK(feat.dim() == 3 && feat.size(0) == B && feat.size(1) == n_agents && feat.size(2) == 16,
-                "coopsearch: grid_features: feat must be [", B, ", ", n_agents, ", 16]");
-    TORCH_CHECK(state.is_cuda(), "coopsearch: grid_features: state must be a GPU tensor");
-    check_f32(state, "state", B * S, state);
+    const char *op = "grid_features";
+    check_team(op, n_agents, side, view_range);
+    check_lookahead(op, lookahead, side);
+    const auto [B, S] = check_rows(op, state, n_agents);
+    check_shape(op, grid, "grid", {B, side * side});
+    check_shape(op, feat, "feat", {B, n_agents, 16});
+    check_lead(op, state, "state", B * S);
     check_dev(grid, "grid", at::kInt, B * side * side, state);
     check_f32(feat, "feat", B * n_agents * 16, state);
     const cs_grid_params p{(int32_t)n_agents, (int32_t)side, (int32_t)view_range, (int32_t)lookahead, (int32_t)S, 0};
@@ -1107,74 +1059,12 @@ void grid_features(const Tensor &state, const Tensor &grid, Tensor feat, int64_t
     TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
 }
 
-// ---- grid observations of recorded episodes (cs_feature_episodes): label_episodes' tensors and integers plus feat [E, T, n, 16]
-// float32 (out); labels is optional here.  Integers and shapes first (nothing is dereferenced), then the tensors.
 void feature_episodes(const Tensor &s, const Tensor &lens, Tensor feat, c10::optional<Tensor> labels, c10::optional<Tensor> grid_out,
                       c10::optional<Tensor> prev_out, int64_t expert, int64_t n_agents, int64_t side, int64_t view_range, int64_t keep,
                       int64_t regrow, int64_t lookahead, int64_t mode, int64_t sense16, int64_t every, int64_t moving, at::IntArrayRef dx,
                       at::IntArrayRef dy) {
-    auto has = [](const c10::optional<Tensor> &t) { return t.has_value() && t->defined(); };
-    TORCH_CHECK(expert == 0 || expert == 1, "coopsearch: feature_episodes: expert must be 0 (coverage) or 1 (belief), got ", expert);
-    TORCH_CHECK(n_agents >= 1 && n_agents <= CS_MAX_AGENTS, "coopsearch: feature_episodes: n_agents must be 1..8, got ", n_agents);
-    TORCH_CHECK(side >= 1 && side <= CS_MAX_MAP, "coopsearch: feature_episodes: side must be 1..", CS_MAX_MAP, ", got ", side);
-    TORCH_CHECK(view_range >= 0 && view_range <= CS_MAX_MAP, "coopsearch: feature_episodes: view_range must be 0..", CS_MAX_MAP, ", got ",
-                view_range);
-    TORCH_CHECK(keep >= 0 && keep <= 65536, "coopsearch: feature_episodes: keep must be 0..65536, got ", keep);
-    TORCH_CHECK(regrow >= 1 && regrow <= 16, "coopsearch: feature_episodes: regrow must be 1..16, got ", regrow);
-    TORCH_CHECK(lookahead >= 0 && lookahead <= side, "coopsearch: feature_episodes: lookahead must be 0..side, got ", lookahead);
-    TORCH_CHECK(mode == CS_MOTION_WALK || mode == CS_MOTION_EVADE, "coopsearch: feature_episodes: mode must be 0 (walk) or 1 (evade), got ", mode);
-    TORCH_CHECK(sense16 >= 0 && sense16 <= 32 * CS_MAX_MAP, "coopsearch: feature_episodes: sense16 must be 0..", 32 * CS_MAX_MAP, ", got ", sense16);
-    TORCH_CHECK(every >= 1 && every <= INT32_MAX, "coopsearch: feature_episodes: every must be >= 1, got ", every);
-    TORCH_CHECK(moving == 0 || moving == 1, "coopsearch: feature_episodes: moving must be 0 or 1, got ", moving);
-    TORCH_CHECK(dx.size() == 16 && dy.size() == 16, "coopsearch: feature_episodes: dx and dy must hold 16 integers each");
-    for (int k = 0; k < 16; k++)
-        TORCH_CHECK(dx[k] >= -16 * CS_MAX_MAP && dx[k] <= 16 * CS_MAX_MAP && dy[k] >= -16 * CS_MAX_MAP && dy[k] <= 16 * CS_MAX_MAP,
-                    "coopsearch: feature_episodes: dx and dy must be -1024..1024, got ", dx[k], " and ", dy[k], " at ", k);
-    TORCH_CHECK(s.dim() == 3 && s.size(0) >= 1 && s.size(0) <= INT32_MAX && s.size(1) >= 1 && s.size(1) <= INT32_MAX &&
-                    s.size(2) >= 4 * n_agents && s.size(2) <= INT32_MAX,
-                "coopsearch: feature_episodes: s must be [E, T, S] with E >= 1, T >= 1 and S >= 4 n_agents = ", 4 * n_agents);
-    const int64_t E = s.size(0), T = s.size(1), S = s.size(2);
-    TORCH_CHECK(lens.dim() == 1 && lens.size(0) == E, "coopsearch: feature_episodes: lens must be [", E, "]");
-    TORCH_CHECK(feat.dim() == 4 && feat.size(0) == E && feat.size(1) == T && feat.size(2) == n_agents && feat.size(3) == 16,
-                "coopsearch: feature_episodes: feat must be [", E, ", ", T, ", ", n_agents, ", 16]");
-    if (has(labels))
-        TORCH_CHECK(labels->dim() == 3 && labels->size(0) == E && labels->size(1) == T && labels->size(2) == n_agents,
-                    "coopsearch: feature_episodes: labels must be [", E, ", ", T, ", ", n_agents, "]");
-    if (has(grid_out))
-        TORCH_CHECK(grid_out->dim() == 2 && grid_out->size(0) == E && grid_out->size(1) == side * side,
-                    "coopsearch: feature_episodes: grid_out must be [", E, ", ", side * side, "]");
-    if (has(prev_out)) {
-        TORCH_CHECK(expert == 1, "coopsearch: feature_episodes: prev_out is the belief filter's (the coverage filter keeps no positions)");
-        TORCH_CHECK(prev_out->dim() == 3 && prev_out->size(0) == E && prev_out->size(1) == CS_MAX_AGENTS && prev_out->size(2) == 2,
-                    "coopsearch: feature_episodes: prev_out must be [", E, ", ", CS_MAX_AGENTS, ", 2]");
-    }
-    TORCH_CHECK(s.is_cuda(), "coopsearch: feature_episodes: s must be a GPU tensor");
-    check_f32(s, "s", E * T * S, s);
-    check_dev(lens, "lens", at::kInt, E, s);
-    check_f32(feat, "feat", E * T * n_agents * 16, s);
-    if (has(labels)) check_dev(*labels, "labels", at::kLong, E * T * n_agents, s);
-    if (has(grid_out)) check_dev(*grid_out, "grid_out", at::kInt, E * side * side, s);
-    if (has(prev_out)) check_dev(*prev_out, "prev_out", at::kInt, E * CS_MAX_AGENTS * 2, s);
-    cs_label_params p{};
-    p.expert = (int32_t)expert;
-    p.n_agents = (int32_t)n_agents;
-    p.side = (int32_t)side;
-    p.view_range = (int32_t)view_range;
-    p.keep = (int32_t)keep;
-    p.regrow = (int32_t)regrow;
-    p.lookahead = (int32_t)lookahead;
-    p.state_width = (int32_t)S;
-    p.mode = (int32_t)mode;
-    p.sense16 = (int32_t)sense16;
-    p.every = (int32_t)every;
-    p.moving = (int32_t)moving;
-    for (int k = 0; k < 16; k++) {
-        p.dx[k] = (int32_t)dx[k];
-        p.dy[k] = (int32_t)dy[k];
-    }
-    const int rc = cs_feature_episodes(&p, s.data_ptr<float>(), (int)E, (int)T, lens.data_ptr<int32_t>(), feat.data_ptr<float>(),
-                                       opt_ptr<int64_t>(labels), opt_ptr<int32_t>(grid_out), opt_ptr<int32_t>(prev_out), stream_of(s));
-    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+    label_on("feature_episodes", "prev_out is the belief filter's (the coverage filter keeps no positions)", s, lens, feat, labels, grid_out,
+             prev_out, expert, n_agents, side, view_range, keep, regrow, lookahead, mode, sense16, every, moving, dx, dy);
 }
 
 }  // namespace

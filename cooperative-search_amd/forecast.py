@@ -133,7 +133,7 @@ class ForecastAgents(pl.PlanAgents):
             self.scores.copy_(scores)
             return actions
         actions = torch.empty(self.batch, self.n_agents, dtype=torch.int64, device=self.device)
-        ops = pl._ops()
+        ops = _lib.torch_ops_for(pl.NEEDS)
         ops.belief_forecast(base.grid, base.prev, self.stack, self.n_agents, self.side, base.model.mode, base.model.sense16,
                             list(base.model.dx), list(base.model.dy), list(moves))
         ops.plan_forecast_actions(state, self.stack, actions, self.plans, self.scores, self.n_agents, self.side, self.view_range,
@@ -141,10 +141,10 @@ class ForecastAgents(pl.PlanAgents):
         return actions
 
     def policy(self):
-        speed, every = self.motion.speed, self.motion.every
+        motion = self.motion
 
         def policy(obs, state, last, t):
             if t == 0:
                 self.reset()
-            return self.choose_action(state, t > 0 and speed > 0 and (t - 1) % every == 0, t)
+            return self.choose_action(state, be.targets_moved(motion, t), t)
         return policy

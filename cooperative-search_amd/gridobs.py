@@ -45,13 +45,7 @@ PROBES = 16                          # per agent: NFEAT of csrc/policy.hip, the 
 SCALE = 2.0 ** -15
 
 
-def _ops():
-    try:
-        return _lib.torch_ops()
-    except _lib.CoopSearchError:
-        raise
-    except Exception as exc:   # noqa: BLE001 -- compiler missing, torch headers missing, dlopen failure
-        raise _lib.CoopSearchError(f"the grid-observation kernels need torch.ops.coopsearch, which is unavailable ({type(exc).__name__}: {exc})") from exc
+NEEDS = "the grid-observation kernels need"   # _lib.torch_ops_for's words
 
 
 def _check(state, grid, n, side, view_range, lookahead):
@@ -104,7 +98,7 @@ def grid_features_hip(state, grid, n_agents, side, view_range, lookahead=None, o
     _check(state, grid, n, side, view_range, lookahead)
     if out is None:
         out = torch.empty(int(state.shape[0]), n, PROBES, dtype=torch.float32, device=state.device)
-    _ops().grid_features(state, grid, out, n, side, view_range, lookahead)
+    _lib.torch_ops_for(NEEDS).grid_features(state, grid, out, n, side, view_range, lookahead)
     return out
 
 
@@ -169,8 +163,9 @@ def feature_episodes_hip(s, lens, expert_params, labels=True, grid_out=True, pre
     lab = torch.empty(E, T, p.n_agents, dtype=torch.int64, device=dev) if labels else None
     grid = torch.empty(E, p.side * p.side, dtype=torch.int32, device=dev) if grid_out else None
     prev = torch.empty(E, _lib.MAX_AGENTS, 2, dtype=torch.int32, device=dev) if (prev_out and p.expert == im.BELIEF) else None
-    _ops().feature_episodes(s, lens, feat, lab, grid, prev, p.expert, p.n_agents, p.side, p.view_range, p.keep, p.regrow, p.lookahead,
-                            p.model.mode, p.model.sense16, p.every, p.moving, list(p.model.dx), list(p.model.dy))
+    ops = _lib.torch_ops_for(NEEDS)
+    ops.feature_episodes(s, lens, feat, lab, grid, prev, p.expert, p.n_agents, p.side, p.view_range, p.keep, p.regrow, p.lookahead,
+                         p.model.mode, p.model.sense16, p.every, p.moving, list(p.model.dx), list(p.model.dy))
     return feat, lab, grid, prev
 
 

@@ -38,13 +38,7 @@ from .collector import EpisodeCollector
 COVERAGE, BELIEF = 0, 1   # cs_label_params.expert
 
 
-def _ops():
-    try:
-        return _lib.torch_ops()
-    except _lib.CoopSearchError:
-        raise
-    except Exception as exc:   # noqa: BLE001 -- compiler missing, torch headers missing, dlopen failure
-        raise _lib.CoopSearchError(f"the imitation kernels need torch.ops.coopsearch, which is unavailable ({type(exc).__name__}: {exc})") from exc
+NEEDS = "the imitation kernels need"   # _lib.torch_ops_for's words
 
 
 # ---- the labeller --------------------------------------------------------------------------------------------------------------
@@ -144,8 +138,9 @@ def label_episodes_hip(s, lens, expert_params, grid_out=True, prev_out=True):
     labels = torch.empty(E, T, p.n_agents, dtype=torch.int64, device=s.device)
     grid = torch.empty(E, p.side * p.side, dtype=torch.int32, device=s.device) if grid_out else None
     prev = torch.empty(E, _lib.MAX_AGENTS, 2, dtype=torch.int32, device=s.device) if (prev_out and p.expert == BELIEF) else None
-    _ops().label_episodes(s, lens, labels, grid, prev, p.expert, p.n_agents, p.side, p.view_range, p.keep, p.regrow, p.lookahead,
-                          p.model.mode, p.model.sense16, p.every, p.moving, list(p.model.dx), list(p.model.dy))
+    ops = _lib.torch_ops_for(NEEDS)
+    ops.label_episodes(s, lens, labels, grid, prev, p.expert, p.n_agents, p.side, p.view_range, p.keep, p.regrow, p.lookahead,
+                       p.model.mode, p.model.sense16, p.every, p.moving, list(p.model.dx), list(p.model.dy))
     return labels, grid, prev
 
 
@@ -262,8 +257,9 @@ class BCLoss(torch.autograd.Function):
         z = f32(logits, rows, A)
         dlogits, stats = torch.empty_like(z), z.new_empty(3)
         scratch = z.new_empty(3 * ((rows + BC_BLOCK - 1) // BC_BLOCK))
-        _ops().bc_loss(z, f32(avail_u, rows, A), labels.detach().reshape(rows).contiguous(), f32(mask, E * T), rows, n, A,
-                       f32(inv_count, 1), dlogits, stats, scratch)
+        ops = _lib.torch_ops_for(NEEDS)
+        ops.bc_loss(z, f32(avail_u, rows, A), labels.detach().reshape(rows).contiguous(), f32(mask, E * T), rows, n, A,
+                    f32(inv_count, 1), dlogits, stats, scratch)
         ctx.save_for_backward(dlogits.view(logits.shape))
         ctx.mark_non_differentiable(stats)
         return stats[0].clone(), stats

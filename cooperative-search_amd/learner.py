@@ -38,6 +38,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _lib
 from .agents import AgentRNN, FusedAgents, rnn_input_shape
 from .replay import expand_compact
 
@@ -59,11 +60,6 @@ def get_mixer_args(args, seed=None):
     return args
 
 
-def _ops():
-    from . import _lib
-    return _lib.torch_ops()
-
-
 def _gru_forward(gi, w_hh, b_hh, h0, save):
     """cs_gru_seq_forward on torch tensors -> (H [T, R, 64], saved [T, R, 4, 64] or None)."""
     T, R = int(gi.shape[0]), int(gi.shape[1])
@@ -73,7 +69,7 @@ def _gru_forward(gi, w_hh, b_hh, h0, save):
     h0 = None if h0 is None else h0.detach().contiguous()
     H = gi.new_empty(T, R, HIDDEN)
     saved = gi.new_empty(T, R, 4, HIDDEN) if save else None
-    _ops().gru_seq_forward(w_hh, b_hh, gi, h0, T, R, H, saved)
+    _lib.torch_ops().gru_seq_forward(w_hh, b_hh, gi, h0, T, R, H, saved)
     return H, saved
 
 
@@ -98,7 +94,7 @@ class GRUSequence(torch.autograd.Function):
         dgi = H.new_empty(T, R, 3 * HIDDEN)
         dgh = H.new_empty(T, R, 3 * HIDDEN)
         dh0 = H.new_empty(R, HIDDEN) if need_h0 else None
-        _ops().gru_seq_backward(w_hh, dH.contiguous(), H, h0, saved, T, R, dgi, dgh, dh0)
+        _lib.torch_ops().gru_seq_backward(w_hh, dH.contiguous(), H, h0, saved, T, R, dgi, dgh, dh0)
         dgh2 = dgh.view(T * R, 3 * HIDDEN)
         dw = db = None
         if need_w:
@@ -142,7 +138,7 @@ def _conv_weights(net):
 def _conv_forward(weights, maps, map_stride, n_maps):
     """policy_conv_features on torch tensors -> feat [n_maps, 16] (no graph)."""
     feat = maps.new_empty(n_maps, CONV_FEATURES)
-    _ops().policy_conv_features(*weights, maps, int(map_stride), int(n_maps), feat)
+    _lib.torch_ops().policy_conv_features(*weights, maps, int(map_stride), int(n_maps), feat)
     return feat
 
 
@@ -181,7 +177,7 @@ class ConvFeatures(torch.autograd.Function):
     def backward(ctx, dfeat):
         maps, *weights = ctx.saved_tensors
         map_stride, n_maps = ctx.geometry
-        ops = _ops()
+        ops = _lib.torch_ops()
         grads = [torch.empty_like(w) for w in weights]
         scratch = _conv_scratch(maps, int(ops.policy_conv_features_backward_scratch(n_maps)))
         ops.policy_conv_features_backward(*weights, maps, map_stride, n_maps, dfeat.contiguous(), *grads, scratch)
@@ -563,7 +559,7 @@ def episode_returns(r, terminated, padded, q=None, gamma=0.99, td_lambda=0.8):
     E, T = int(r.shape[0]), int(r.shape[1])
     flat = lambda x: x.detach().float().reshape(E, T).contiguous()
     out = torch.empty(E, T, dtype=torch.float32, device=r.device)
-    _ops().episode_returns(flat(r), flat(terminated), flat(padded), None if q is None else flat(q), E, T, float(gamma),
+    _lib.torch_ops().episode_returns(flat(r), flat(terminated), flat(padded), None if q is None else flat(q), E, T, float(gamma),
                            float(td_lambda), out)
     return out
 
@@ -843,7 +839,7 @@ def gae(r, terminated, padded, v, v_next, gamma=0.99, gae_lambda=0.95):
     flat = lambda x: x.detach().float().reshape(E, T).contiguous()
     adv = torch.empty(E, T, dtype=torch.float32, device=r.device)
     ret = torch.empty_like(adv)
-    _ops().gae(flat(r), flat(terminated), flat(padded), flat(v), flat(v_next), E, T, float(gamma), float(gae_lambda), adv, ret)
+    _lib.torch_ops().gae(flat(r), flat(terminated), flat(padded), flat(v), flat(v_next), E, T, float(gamma), float(gae_lambda), adv, ret)
     return adv, ret
 
 
@@ -897,7 +893,7 @@ def ppo_logp(logits, avail_u, u, mask, epsilon):
     no-grad mode: the instructions that compute logp inside PPOPolicyLoss, so an unchanged policy has ratio exactly 1."""
     z, av, uu, m, rows, n, A, eps, eps_t = _ppo_rows(logits, avail_u, u, mask, epsilon)
     out = z.new_empty(rows)
-    _ops().ppo_loss(z, av, uu, None, None, m, rows, n, A, 0.0, 0.0, eps, eps_t, None, None, out, None, None)
+    _lib.torch_ops().ppo_loss(z, av, uu, None, None, m, rows, n, A, 0.0, 0.0, eps, eps_t, None, None, out, None, None)
     return out.view(logits.shape[:3])
 
 
@@ -915,7 +911,7 @@ class PPOPolicyLoss(torch.autograd.Function):
         f32 = lambda x, k: x.detach().float().reshape(k).contiguous()
         dlogits, stats = torch.empty_like(z), z.new_empty(4)
         scratch = z.new_empty(4 * ((rows + PPO_BLOCK - 1) // PPO_BLOCK))
-        _ops().ppo_loss(z, av, uu, f32(old_logp, rows), f32(adv, rows // n), m, rows, n, A, float(clip), float(ent_coef), eps, eps_t,
+        _lib.torch_ops().ppo_loss(z, av, uu, f32(old_logp, rows), f32(adv, rows // n), m, rows, n, A, float(clip), float(ent_coef), eps, eps_t,
                         f32(inv_count, 1), dlogits, None, stats, scratch)
         ctx.save_for_backward(dlogits.view(logits.shape))
         ctx.mark_non_differentiable(stats)

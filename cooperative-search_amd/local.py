@@ -22,7 +22,8 @@ look-ahead footprints, the tie rule and the action coding -- but for the links:
 """
 import torch
 
-from .baseline import FRESH, HEADINGS, _check_params, _ops, keep_of, quantise, trig_tables
+from .baseline import (FRESH, GridAgents, _check_params, _check_state_grid, cell_centres, disc_mask, greedy_choose, keep_of, quantise,
+                       trig_tables)
 
 MAX_COMM = 128   # LOC_MAX_COMM of csrc/local.h, in cells (a 64-cell map's diagonal is under 91)
 
@@ -30,13 +31,6 @@ MAX_COMM = 128   # LOC_MAX_COMM of csrc/local.h, in cells (a 64-cell map's diago
 def _check_comm(comm_range):
     if not -1 <= comm_range <= MAX_COMM:
         raise ValueError(f"local coverage: comm_range must be -1 (unlimited) or 0..{MAX_COMM} cells, got {comm_range!r}")
-
-
-def _check_tensors(state, grids, n, side):
-    if state.dim() != 2 or state.dtype != torch.float32 or state.shape[0] < 1 or state.shape[1] < 4 * n:
-        raise ValueError(f"local coverage: state must be float32 [B, S] with B >= 1 and S >= 4 n_agents = {4 * n}")
-    if grids.dtype != torch.int32 or tuple(grids.shape) != (state.shape[0], n, side * side) or grids.device != state.device:
-        raise ValueError(f"local coverage: grids must be int32 [{state.shape[0]}, {n}, {side * side}] on the state's device")
 
 
 def links(X, Y, comm_range):
@@ -72,79 +66,32 @@ def local_coverage_actions_torch(state, grids, n_agents, side, view_range, keep,
     lookahead = min(view_range, side) if lookahead is None else int(lookahead)
     _check_params(n, side, view_range, keep, regrow, lookahead)
     _check_comm(comm_range)
-    _check_tensors(state, grids, n, side)
-    i64, dev = torch.int64, state.device
-    B, R2 = int(state.shape[0]), (16 * view_range) ** 2
+    _check_state_grid("local coverage", state, grids, n, (n, side * side), name="grids")
     X, Y, h = quantise(state, n, side)
     adj = links(X, Y, comm_range)
-    centre = (16 * torch.arange(side, dtype=i64, device=dev) + 8).view(1, side)
-
-    def within(px, py):   # [B] points -> [B, cells], cell ix * side + iy
-        dx, dy = centre - px.view(B, 1), centre - py.view(B, 1)
-        return ((dx * dx).view(B, side, 1) + (dy * dy).view(B, 1, side) <= R2).view(B, side * side)
-
-    G = grids.to(i64).clamp(0, FRESH)   # [B, n, cells]
+    centre, R2 = cell_centres(side, state.device), (16 * view_range) ** 2
+    G = grids.to(torch.int64).clamp(0, FRESH)   # [B, n, cells]
     G = G + ((FRESH - G) >> regrow)
-    own = torch.stack([within(X[:, i], Y[:, i]) for i in range(n)], 1)
+    own = torch.stack([disc_mask(centre, X[:, i], Y[:, i], R2) for i in range(n)], 1)
     S = torch.where(own, (G * keep) >> 16, G)
     far = torch.full_like(S, FRESH + 1)   # above every cell: an agent that is not heard does not enter the minimum
     M = torch.stack([torch.where(adj[:, i, :, None], S, far).min(1).values for i in range(n)], 1)
     grids.copy_(M.to(torch.int32))
-    ct, st = trig_tables()
-    offx = torch.tensor([(lookahead * 16 * v) >> 14 for v in ct], dtype=i64, device=dev)   # (Python's >> floors)
-    offy = torch.tensor([(lookahead * 16 * v) >> 14 for v in st], dtype=i64, device=dev)
-    zero = torch.zeros(B, side * side, dtype=i64, device=dev)
-    actions = torch.empty(B, n, dtype=i64, device=dev)
-    scores = torch.empty(B, n, 3, dtype=i64, device=dev)
-    claims = []
-    for i in range(n):
-        W = M[:, i]
-        for j in range(i):   # the claims agent i has heard
-            W = torch.where(claims[j] & adj[:, i, j].view(B, 1), zero, W)
-        foot, score = [], []
-        for turn in (0, 1, HEADINGS - 1):
-            hp = (h[:, i] + turn) % HEADINGS
-            px = torch.clamp(X[:, i] + offx[hp], 0, 16 * side)
-            py = torch.clamp(Y[:, i] + offy[hp], 0, 16 * side)
-            foot.append(within(px, py))
-            score.append(torch.where(foot[-1], W, zero).sum(1))
-        best = (score[1] > score[0]).to(i64)
-        best = torch.where(score[2] > torch.maximum(score[0], score[1]), torch.full_like(best, 2), best)
-        actions[:, i] = best
-        scores[:, i] = torch.stack(score, 1)
-        claims.append(torch.where((best == 0).view(B, 1), foot[0], torch.where((best == 1).view(B, 1), foot[1], foot[2])))
+    actions, scores = greedy_choose(M, X, Y, h, side, view_range, lookahead, adj)
     return (actions, scores) if return_scores else actions
 
 
-class LocalCoverageAgents:
-    """The coverage baseline under a communication range, for a batch of envs.  env_or_args, batch, device, lookahead, regrow and
-    impl are CoverageAgents'; comm_range is in whole cells, 0..128, None = unlimited.  impl = "hip": the kernel of csrc/local.h, one
-    launch per `choose_action` on the current stream, no synchronisation; "torch": the definition, on the same device.
+class LocalCoverageAgents(GridAgents):
+    """The coverage baseline under a communication range, for a batch of envs: CoverageAgents' arguments, and comm_range in whole
+    cells, 0..128, None = unlimited.
 
-    `.grids` is int32 [B, n, side * side]: agent i's private grid.  `policy()` is a `policy(obs, state, last, t)` callable for
-    EpisodeCollector.generate_episodes(policy=...), collector.evaluate and collector.collect_experiment_data; it resets the grids
-    when t == 0.  With comm_range None it flies CoverageAgents' episodes; with 0, n lone agents'."""
+    `.grids` is int32 [B, n, side * side]: agent i's private grid; `policy()` resets them when t == 0.  With comm_range None it
+    flies CoverageAgents' episodes; with 0, n lone agents'."""
+    KERNEL, NEEDS = "local.h", "the coverage kernel needs"
 
     def __init__(self, env_or_args, comm_range, batch=None, device=None, lookahead=None, regrow=8, impl="hip"):
-        src = env_or_args
-        if impl not in ("hip", "torch"):
-            raise ValueError("impl must be 'hip' (the kernel of csrc/local.h) or 'torch' (the definition)")
-        batch = getattr(src, "batch", None) if batch is None else batch
-        if batch is None or int(batch) < 1:
-            raise ValueError("LocalCoverageAgents: batch must be given (>= 1) with an args namespace")
-        self.batch = int(batch)
-        self.device = torch.device(device if device is not None else getattr(src, "device", "cuda"))
-        if impl == "hip" and self.device.type != "cuda":
-            raise ValueError(f"LocalCoverageAgents(impl='hip') runs a HIP kernel and {self.device} is not a GPU: there is no CPU "
-                             "fallback (impl='torch' runs the definition anywhere)")
-        self.impl = impl
-        self.n_agents, self.side = int(src.n_agents), int(src.map_size)
-        if int(src.view_range) != src.view_range:
-            raise ValueError(f"LocalCoverageAgents: view_range must be a whole number of cells, got {src.view_range!r}")
-        self.view_range = int(src.view_range)
-        self.keep = keep_of(src.detect_prob)
+        super().__init__(env_or_args, batch, device, lookahead, impl)
         self.regrow = int(regrow)
-        self.lookahead = min(self.view_range, self.side) if lookahead is None else int(lookahead)
         _check_params(self.n_agents, self.side, self.view_range, self.keep, self.regrow, self.lookahead)
         if comm_range is not None and (int(comm_range) != comm_range or comm_range < 0):
             raise ValueError(f"LocalCoverageAgents: comm_range must be a whole number of cells, 0..{MAX_COMM}, or None (unlimited), "
@@ -162,16 +109,7 @@ class LocalCoverageAgents:
         if self.impl == "torch":
             return local_coverage_actions_torch(state, self.grids, self.n_agents, self.side, self.view_range, self.keep, self.comm_range,
                                                 self.regrow, self.lookahead)
-        if not torch.is_tensor(state) or state.dim() != 2 or int(state.shape[0]) != self.batch:
-            raise ValueError(f"LocalCoverageAgents: state must be a [{self.batch}, S] tensor")
-        actions = torch.empty(self.batch, self.n_agents, dtype=torch.int64, device=self.device)
-        _ops().local_coverage_actions(state, self.grids, actions, self.n_agents, self.side, self.view_range, self.keep, self.regrow,
-                                      self.lookahead, self.comm_range)
+        ops, actions = self._launch(state)
+        ops.local_coverage_actions(state, self.grids, actions, self.n_agents, self.side, self.view_range, self.keep, self.regrow,
+                                   self.lookahead, self.comm_range)
         return actions
-
-    def policy(self):
-        def policy(obs, state, last, t):
-            if t == 0:
-                self.reset()
-            return self.choose_action(state)
-        return policy

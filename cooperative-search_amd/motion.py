@@ -28,6 +28,7 @@ slot j:
 step t and a policy acts without knowing the coming move.
 """
 import dataclasses
+import functools
 import math
 
 import torch
@@ -212,13 +213,8 @@ def split_runs(phase, T, every):
     return runs
 
 
-def _ops():
-    try:
-        return _lib.torch_ops()
-    except _lib.CoopSearchError:
-        raise
-    except Exception as exc:   # noqa: BLE001 -- compiler missing, torch headers missing, dlopen failure
-        raise _lib.CoopSearchError(f"the target-motion kernel needs torch.ops.coopsearch, which is unavailable ({type(exc).__name__}: {exc})") from exc
+# the op layer, _lib.torch_ops(), with this module's words for a failure to load it; a module attribute, so that a test can wrap it
+_ops = functools.partial(_lib.torch_ops_for, "the target-motion kernel needs")
 
 
 def move_targets(env, motion, env_offset=None):

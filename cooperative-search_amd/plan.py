@@ -39,6 +39,7 @@ CAP = 1 << 19          # a cell is read as clamp(cell, 0, CAP)
 MAX_DEPTH = 5          # CS_PLAN_MAX_DEPTH: 3^5 = 243 sequences, 363 nodes
 MAX_STRIDE = 8
 TURN = (0, 1, bl.HEADINGS - 1)
+NEEDS = "the plan kernel needs"   # _lib.torch_ops_for's words, forecast.py's too
 _CHUNK = 1 << 24       # the definition works on at most this many (env, sequence, cell) triples at a time (envs are independent)
 
 
@@ -57,8 +58,7 @@ def weights(depth, discount):
 
 
 def _check_params(n, side, view_range, depth, stride, discount):
-    if not 1 <= n <= _lib.MAX_AGENTS or not 1 <= side <= bl.MAX_MAP or not 0 <= view_range <= bl.MAX_MAP:
-        raise ValueError(f"plan: n_agents must be 1..{_lib.MAX_AGENTS}, side 1..{bl.MAX_MAP} and view_range 0..{bl.MAX_MAP}")
+    bl._check_team("plan", n, side, view_range)
     if not 1 <= depth <= MAX_DEPTH or not 1 <= stride <= MAX_STRIDE or not 0 <= discount <= 256:
         raise ValueError(f"plan: depth must be 1..{MAX_DEPTH}, stride 1..{MAX_STRIDE} and discount 0..256")
 
@@ -66,10 +66,7 @@ def _check_params(n, side, view_range, depth, stride, discount):
 def _check_tensors(state, grid, n, side):
     if not torch.is_tensor(state) or not torch.is_tensor(grid):
         raise TypeError("plan: state and grid must be tensors")
-    if state.dim() != 2 or state.dtype != torch.float32 or state.shape[0] < 1 or state.shape[1] < 4 * n:
-        raise ValueError(f"plan: state must be float32 [B, S] with B >= 1 and S >= 4 n_agents = {4 * n}")
-    if grid.dtype != torch.int32 or tuple(grid.shape) != (state.shape[0], side * side) or grid.device != state.device:
-        raise ValueError(f"plan: grid must be int32 [{state.shape[0]}, {side * side}] on the state's device")
+    bl._check_state_grid("plan", state, grid, n, (side * side,))
 
 
 def _plan_rows(state, levels, n, side, view_range, depth, stride, discount):
@@ -78,14 +75,10 @@ def _plan_rows(state, levels, n, side, view_range, depth, stride, discount):
     i64, dev = torch.int64, state.device
     B, R2, lim, cells = int(state.shape[0]), (16 * view_range) ** 2, 16 * side, side * side
     X, Y, h = bl.quantise(state, n, side)
-    centre = 16 * torch.arange(side, dtype=i64, device=dev) + 8
+    centre = bl.cell_centres(side, dev)
     sx, sy = (torch.tensor(t, dtype=i64, device=dev) for t in step_tables())
     turn = torch.tensor(TURN, dtype=i64, device=dev)
     w = weights(depth, discount)
-
-    def within(px, py):   # [B, N] points -> [B, N, cells], cell ix * side + iy
-        dx, dy = centre - px.unsqueeze(-1), centre - py.unsqueeze(-1)
-        return ((dx * dx).unsqueeze(-1) + (dy * dy).unsqueeze(-2) <= R2).reshape(B, -1, cells)
 
     W = levels.to(i64).clamp(0, CAP)
     last = W.shape[1] - 1
@@ -104,7 +97,7 @@ def _plan_rows(state, levels, n, side, view_range, depth, stride, discount):
                 x = torch.clamp(x + sx[hh], 0, lim)
                 y = torch.clamp(y + sy[hh], 0, lim)
             covered = covered.repeat_interleave(3, dim=1)
-            disc = within(x, y)
+            disc = bl.disc_mask(centre, x, y, R2)
             gain = torch.where(disc & ~covered, W[:, min(d, last)].unsqueeze(1), zero).sum(-1)     # [B, 3^(d + 1)]
             score = score.repeat_interleave(3, dim=1) + gain * w[d]
             covered = covered | disc
@@ -132,15 +125,6 @@ def plan_actions_torch(state, grid, n_agents, side, view_range, depth, stride, d
              for b in range(0, int(state.shape[0]), rows)]
     actions, plans, scores = (torch.cat(t) for t in zip(*parts))
     return (actions, plans, scores) if return_plans else actions
-
-
-def _ops():
-    try:
-        return _lib.torch_ops()
-    except _lib.CoopSearchError:
-        raise
-    except Exception as exc:   # noqa: BLE001 -- compiler missing, torch headers missing, dlopen failure
-        raise _lib.CoopSearchError(f"the plan kernel needs torch.ops.coopsearch, which is unavailable ({type(exc).__name__}: {exc})") from exc
 
 
 class PlanAgents:
@@ -210,15 +194,15 @@ class PlanAgents:
             self.scores.copy_(scores)
             return actions
         actions = torch.empty(self.batch, self.n_agents, dtype=torch.int64, device=self.device)
-        _ops().plan_actions(state, self.base.grid, actions, self.plans, self.scores, self.n_agents, self.side, self.view_range,
-                            self.depth, self.stride, self.discount)
+        _lib.torch_ops_for(NEEDS).plan_actions(state, self.base.grid, actions, self.plans, self.scores, self.n_agents, self.side,
+                                               self.view_range, self.depth, self.stride, self.discount)
         return actions
 
     def policy(self):
-        speed, every = self.motion.speed, self.motion.every
+        motion = self.motion
 
         def policy(obs, state, last, t):
             if t == 0:
                 self.reset()
-            return self.choose_action(state, t > 0 and speed > 0 and (t - 1) % every == 0)
+            return self.choose_action(state, be.targets_moved(motion, t))
         return policy

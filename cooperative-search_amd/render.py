@@ -260,15 +260,6 @@ def render_episodes_torch(states, maps, counts, spec):
     return out
 
 
-def _ops():
-    try:
-        return _lib.torch_ops()
-    except _lib.CoopSearchError:
-        raise
-    except Exception as exc:   # noqa: BLE001 -- compiler missing, torch headers missing, dlopen failure
-        raise _lib.CoopSearchError(f"episode frames need torch.ops.coopsearch, which is unavailable ({type(exc).__name__}: {exc})") from exc
-
-
 _device_tables = {}
 
 
@@ -299,8 +290,8 @@ def render_episodes(states, maps, counts, spec, out=None):
     pal, lut = _palette_lut(spec, states.device)
     if counts.dtype != torch.int32:
         counts = counts.to(torch.int32)
-    _ops().render_episodes(states, maps, counts, int(spec.n_agents), m, side, W, list(spec.radii()), spec.layers(), spec.colours(),
-                           pal, lut, out)
+    ops = _lib.torch_ops_for("episode frames need")
+    ops.render_episodes(states, maps, counts, int(spec.n_agents), m, side, W, list(spec.radii()), spec.layers(), spec.colours(), pal, lut, out)
     return out
 
 

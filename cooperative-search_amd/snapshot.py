@@ -17,15 +17,6 @@ FORMAT_VERSION = 1   # CS_SNAPSHOT_VERSION
 META_FIELDS = ("variant", "n_agents", "n_targets", "map_size", "version")
 
 
-def _ops():
-    try:
-        return _lib.torch_ops()
-    except _lib.CoopSearchError:
-        raise
-    except Exception as exc:   # noqa: BLE001 -- compiler missing, torch headers missing, dlopen failure
-        raise _lib.CoopSearchError(f"env snapshots need torch.ops.coopsearch, which is unavailable ({type(exc).__name__}: {exc})") from exc
-
-
 def env_meta(env):
     """What a record of `env` is bound to."""
     return dict(variant=str(env.variant), n_agents=int(env.n_agents), n_targets=int(env.target_num), map_size=int(env.map_size),
@@ -85,7 +76,7 @@ def _index(idx, env, name):
 def snapshot(env, envs=None):
     """Records of the envs `envs` (int64 indices; None: all, in order) of a BatchedFlightEnv.  The env is only read; nothing
     synchronises when `envs` is None or a device tensor."""
-    ops = _ops()
+    ops = _lib.torch_ops_for("env snapshots need")
     meta = env_meta(env)
     idx = _index(envs, env, "envs")
     count = env.batch if idx is None else int(idx.numel())
@@ -100,7 +91,7 @@ def restore(env, snap, src=None, dst=None, status=None):
     mismatch raises ValueError before anything is launched.  The live get_obs() / get_state() buffers are refreshed and the next
     step() refreshes the hit tapes.  `status` (int32 [4] on the env's device) receives cs_restore's verdict on the indices and
     record headers: {0, -1, -1, 0}, or {1, kind, entry, value} for the first refused entry, whose env stays untouched."""
-    ops = _ops()
+    ops = _lib.torch_ops_for("env snapshots need")
     snap.check(env_meta(env))
     src, dst = _index(src, env, "src"), _index(dst, env, "dst")
     if src is not None and dst is not None and src.numel() != dst.numel():

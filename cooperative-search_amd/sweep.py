@@ -31,8 +31,7 @@ SweepResult = collections.namedtuple("SweepResult", ["first", "new_cells", "seen
 
 
 def _check_params(n, side, view_range):
-    if not 1 <= n <= _lib.MAX_AGENTS or not 1 <= side <= _bl.MAX_MAP or not 0 <= view_range <= _bl.MAX_MAP:
-        raise ValueError(f"sweep: n_agents must be 1..{_lib.MAX_AGENTS}, side 1..{_bl.MAX_MAP} and view_range 0..{_bl.MAX_MAP}")
+    _bl._check_team("sweep", n, side, view_range)
 
 
 def _check(states, counts, n, side, view_range):
@@ -51,40 +50,23 @@ def sweep_episodes_torch(states, counts, n_agents, side, view_range):
     quantisation must not be contracted into a fused multiply-add: see baseline.coverage_actions_torch)."""
     n, side, view_range = int(n_agents), int(side), int(view_range)
     _check(states, counts, n, side, view_range)
-    i64, dev = torch.int64, states.device
+    dev = states.device
     E, T1, S = (int(v) for v in states.shape)
     R2 = (16 * view_range) ** 2
     X, Y = _bl.quantise_positions(states.reshape(E * T1, S), n, side)
     X, Y = X.view(E, T1, n), Y.view(E, T1, n)
-    centre = (16 * torch.arange(side, dtype=i64, device=dev) + 8).view(1, side)
-    valid = torch.arange(T1, dtype=i64, device=dev).view(1, T1) < counts.to(i64).clamp(0, T1).view(E, 1)   # [E, T1]
-
-    def within(px, py):   # [E] points -> [E, cells], cell ix * side + iy
-        dx, dy = centre - px.view(E, 1), centre - py.view(E, 1)
-        return ((dx * dx).view(E, side, 1) + (dy * dy).view(E, 1, side) <= R2).view(E, side * side)
-
+    centre = _bl.cell_centres(side, dev)
+    valid = torch.arange(T1, dtype=torch.int64, device=dev).view(1, T1) < counts.to(torch.int64).clamp(0, T1).view(E, 1)   # [E, T1]
     first = torch.full((E, side * side), -1, dtype=torch.int32, device=dev)
     new_cells = torch.zeros(E, T1, dtype=torch.int32, device=dev)
     seen_cells = torch.zeros(E, T1, dtype=torch.int32, device=dev)
     for t in range(T1):
-        seen = within(X[:, t, 0], Y[:, t, 0])
-        for i in range(1, n):
-            seen = seen | within(X[:, t, i], Y[:, t, i])
-        seen = seen & valid[:, t].view(E, 1)
+        seen = _bl.swept(centre, X[:, t], Y[:, t], R2) & valid[:, t].view(E, 1)
         fresh = seen & (first < 0)
         first = torch.where(fresh, torch.full_like(first, t), first)
         new_cells[:, t] = fresh.sum(1)
         seen_cells[:, t] = seen.sum(1)
     return SweepResult(first, new_cells, seen_cells)
-
-
-def _ops():
-    try:
-        return _lib.torch_ops()
-    except _lib.CoopSearchError:
-        raise
-    except Exception as exc:   # noqa: BLE001 -- compiler missing, torch headers missing, dlopen failure
-        raise _lib.CoopSearchError(f"the sweep kernel needs torch.ops.coopsearch, which is unavailable ({type(exc).__name__}: {exc})") from exc
 
 
 def _impl_for(tensor, impl):
@@ -113,7 +95,8 @@ def sweep_episodes(states, counts, n_agents, side, view_range, impl="hip"):
     dev = states.device
     out = SweepResult(torch.empty(E, side * side, dtype=torch.int32, device=dev), torch.empty(E, T1, dtype=torch.int32, device=dev),
                       torch.empty(E, T1, dtype=torch.int32, device=dev))
-    _ops().sweep_episodes(states, counts, out.first, out.new_cells, out.seen_cells, n, side, view_range)
+    _lib.torch_ops_for("the sweep kernel needs").sweep_episodes(states, counts, out.first, out.new_cells, out.seen_cells, n, side,
+                                                                view_range)
     return out
 
 
