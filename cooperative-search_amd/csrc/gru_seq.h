@@ -149,19 +149,53 @@ __global__ __launch_bounds__(GBLOCK) void k_gru_seq_fwd(GruFwdParams p) {
     }
 }
 
+// |v| of a finite v, 0 of an inf or a NaN: what the block's scale may look at
+__device__ __forceinline__ float finite_abs(float v) {
+    const float a = fabsf(v);
+    return a < __builtin_inff() ? a : 0.0f;
+}
+// 2^k as a float, -126 <= k <= 127
+__device__ __forceinline__ float pow2f_(int k) { return __int_as_float((127 + k) << 23); }
+// largest of a non-negative int over the wavefront, in every lane's hands as a scalar: quads, half rows and rows by DPP (register
+// to register, no LDS), then the four rows of 16 lanes through scalar registers
+__device__ __forceinline__ int wave_max_nonneg(int v) {
+    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));    // quad_perm [1, 0, 3, 2]
+    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false));    // quad_perm [2, 3, 0, 1]
+    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false));   // row_half_mirror
+    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false));   // row_mirror
+    return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+               max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+constexpr int NO_EXP = -(1 << 20);   // s_exp of a wavefront whose dgh_t holds no finite non-zero value
+
 // Backward, t = T-1 .. 0.  Wavefront w owns hidden units 16w..16w+15 again: with dh = dH_t + carry it forms the gate adjoints of its
 // units (dgi_t = [da_r, da_z, da_n], dgh_t = [da_r, da_z, da_n r]), writes them out and into LDS (split), and after the barrier
 // multiplies the whole dgh_t row tile (K = 192) by ITS 16 columns of W_hh: carry = dh z + dgh_t W_hh, output tile w -- the same
 // (row, unit) elements the lane owns, so the carry never leaves its registers.  6 k-steps x 3 = 18 MFMAs per step, as two
 // independent accumulator pairs (even / odd k-steps).
 //
-// Scaling: gradients have no natural scale, and the split-fp16 operands keep 22 significant bits only inside fp16's normal range.
-// Each block therefore first reads its rows of dH once and runs the recurrence on dH * 2^s, with s chosen so that the largest |dH|
-// lies in [32, 64); every output is multiplied by 2^-s on its way out.  The scaling by a power of two is exact: it only moves the
-// block's values into the range the matrix path represents with full precision.
+// Scaling: gradients have no natural scale, and the split-fp16 operands keep 22 significant bits only inside fp16's normal range
+// and SATURATE at +-65504 (split_f16).  The block therefore runs its recurrence on (true value) * 2^s and multiplies every output
+// by 2^-s on its way out; powers of two, so the scaling itself is exact.  s starts at s0, chosen from one pass over the block's
+// rows of dH so that the largest finite |dH| lies in [32, 64).  dH alone does not bound what goes through the matrix path: that is
+// dgh_t, formed from dH_t 2^s + carry, and the carry can grow along the recurrence by many orders of magnitude (same-sign
+// gradients, |W_hh| large).  So s FOLLOWS dgh: in the shadow of step t's MFMAs every wavefront reduces the largest finite
+// |dgh_t| and |dh| of its elements (dh too: it is what the carry hands on through dh z when every gate of a step is saturated
+// and dgh_t all but vanishes; registers, DPP, no LDS traffic) and publishes its exponent in TRUE units (minus s: an integer, so it
+// cannot overflow) in s_exp[t & 1][w]; the barrier of step t - 1 makes the four values visible, and at the end of step t - 1
+// the carry is moved by an exact power of two to s = min(s0 + 5, 5 - E_t), E_t that exponent: the largest |dgh| or |dh| of
+// two steps earlier lies in [32, 64), which leaves a factor of 1023 for the growth over TWO STEPS (not, as a scale fixed from dH
+// would, over the whole recurrence; the lag spares a second barrier per step, the instructions themselves are not free: measured
+// +0.14 us per step, 304 -> 333 us per launch at T = 200).  s may rise above s0 when
+// the carry decays (dH concentrated on the last steps), but by 2^5 at the most, so dH_t 2^s never exceeds 2048 whatever comes.
+// Below the largest value the planes resolve 2^-35 absolutely (the lo plane's subnormal halves): a block has ONE scale, and a row
+// much smaller than the block's largest is accurate relative to that row, not to itself.  Non-finite values are left out of both
+// maxima, element by element: a row that carries an inf or a NaN keeps it (rows do not mix in the products) and the block's other rows keep their
+// scale.  No atomics, nothing depends on the grid.
 __global__ __launch_bounds__(GBLOCK) void k_gru_seq_bwd(GruBwdParams p) {
     __shared__ __attribute__((aligned(16))) _Float16 s_g[2][2][16 * GST];   // [step parity][hi, lo]: dgh_t
     __shared__ float s_max[4];
+    __shared__ __attribute__((aligned(16))) int s_exp[2][4];   // [step parity][wavefront]: exponent of the wavefront's largest finite |dgh_t|, true units
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int crow = (lane >> 4) * 4, col = 16 * w + (lane & 15);
     const int row0 = 16 * blockIdx.x;
@@ -184,22 +218,25 @@ __global__ __launch_bounds__(GBLOCK) void k_gru_seq_bwd(GruBwdParams p) {
         if (srow < p.rows)
             for (int t = 0; t < p.T; t++) {
                 const float *v = p.dh_seq + ((size_t)t * p.rows + srow) * H + k4;
-                m = fmaxf(m, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
+                m = fmaxf(m, fmaxf(fmaxf(finite_abs(v[0]), finite_abs(v[1])), fmaxf(finite_abs(v[2]), finite_abs(v[3]))));
             }
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
         if (lane == 0) s_max[w] = m;
+        if (threadIdx.x < 8) (&s_exp[0][0])[threadIdx.x] = NO_EXP;
     }
     __syncthreads();
     const float m = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
-    float scale = 1.0f, unscale = 1.0f;
-    if (m > 0.0f && m <= 3.0e38f) {
+    int s0 = 0;   // m == 0 (no finite non-zero dH): scale 1
+    if (m > 0.0f) {
         int e;
         frexpf(m, &e);          // m = f 2^e, f in [0.5, 1)
         e = e < -120 ? -120 : e;
-        scale = ldexpf(1.0f, 6 - e);
-        unscale = ldexpf(1.0f, e - 6);
+        s0 = 6 - e;             // -122 .. 126: 2^s0 and 2^-s0 are normal floats
     }
+    const int s_cap = min(s0 + 5, 126);
+    int s = __builtin_amdgcn_readfirstlane(s0);
+    float scale = pow2f_(s), unscale = pow2f_(-s);
 
     size_t rowc[4];
     bool valid[4];
@@ -231,7 +268,7 @@ __global__ __launch_bounds__(GBLOCK) void k_gru_seq_bwd(GruBwdParams p) {
     for (int t = p.T - 1; t >= 0; t--) {
         const int buf = t & 1;
         if (t > 0) fetch(t - 1, nxt);   // block-uniform; first used at the end of the step
-        float dhz[4];
+        float dhz[4], g[4][4];   // g: dgh_t and dh of the lane's elements, kept for the scale's maximum (taken after the barrier)
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const float dh = __builtin_fmaf(cur.dh[r], scale, carry[r]);   // exact product: scale is a power of two
@@ -242,6 +279,10 @@ __global__ __launch_bounds__(GBLOCK) void k_gru_seq_bwd(GruBwdParams p) {
             const float daz = dz * (zg * (1.0f - zg));
             const float dghn = dan * rg;
             dhz[r] = dh * zg;
+            g[0][r] = dar;
+            g[1][r] = daz;
+            g[2][r] = dghn;
+            g[3][r] = dh;
             split_store(s_g[buf][0], s_g[buf][1], (crow + r) * GST + col, dar);
             split_store(s_g[buf][0], s_g[buf][1], (crow + r) * GST + H + col, daz);
             split_store(s_g[buf][0], s_g[buf][1], (crow + r) * GST + 2 * H + col, dghn);
@@ -256,6 +297,7 @@ __global__ __launch_bounds__(GBLOCK) void k_gru_seq_bwd(GruBwdParams p) {
             }
         }
         __syncthreads();   // dgh_t complete in s_g[buf] (last read in step t + 2, before the previous barrier)
+        const int4 e4 = *reinterpret_cast<const int4 *>(s_exp[buf ^ 1]);   // step t + 1's exponents: read first, used last
         f32x4 hi0 = {dhz[0], dhz[1], dhz[2], dhz[3]}, lo0 = zero, hi1 = zero, lo1 = zero;
 #pragma unroll
         for (int ks = 0; ks < 6; ks += 2) {
@@ -265,8 +307,25 @@ __global__ __launch_bounds__(GBLOCK) void k_gru_seq_bwd(GruBwdParams p) {
             mfma_split(ah0, al0, wf[ks], hi0, lo0);
             mfma_split(ah1, al1, wf[ks + 1], hi1, lo1);
         }
+        // the scale follows dgh (see above): publish this step's exponent, adopt the one of the step before (visible since the
+        // barrier).  All of it here, among the MFMAs, where vector instructions are nearly free -- not before the barrier
+        {
+            float big = 0.0f;
 #pragma unroll
-        for (int r = 0; r < 4; r++) carry[r] = split_sum(hi0[r] + hi1[r], lo0[r] + lo1[r]);
+            for (int r = 0; r < 4; r++) {
+                asm volatile("" : "+v"(g[0][r]), "+v"(g[1][r]), "+v"(g[2][r]), "+v"(g[3][r]));
+                big = fmaxf(fmaxf(big, finite_abs(g[3][r])), fmaxf(fmaxf(finite_abs(g[0][r]), finite_abs(g[1][r])), finite_abs(g[2][r])));
+            }
+            const int mb = wave_max_nonneg(__float_as_int(big));   // bits of a finite float >= 0: ordered like the floats
+            if (lane == 0) s_exp[buf][w] = mb ? (mb >> 23) - 127 - s : NO_EXP;
+        }
+        const int E = __builtin_amdgcn_readfirstlane(max(max(e4.x, e4.y), max(e4.z, e4.w)));   // NO_EXP at t = T - 1
+        const int s_next = E != NO_EXP ? min(s_cap, max(5 - E, -122)) : s;
+#pragma unroll
+        for (int r = 0; r < 4; r++) carry[r] = ldexpf(split_sum(hi0[r] + hi1[r], lo0[r] + lo1[r]), s_next - s);   // exact: 2^(s' - s)
+        s = s_next;
+        scale = pow2f_(s);
+        unscale = pow2f_(-s);
         // first use of the next step's inputs: here (see the forward)
 #pragma unroll
         for (int r = 0; r < 4; r++) {
