@@ -24,6 +24,7 @@ from .sweep import SweepResult, sweep_episodes, sweep_episodes_torch, sweep_batc
 from .sweep import sweep_bonus, with_sweep_bonus, collect_sweep_data  # noqa: F401
 from .motion import TargetMotion, MovingTargetEnv, move_targets_torch, make_env  # noqa: F401
 from .belief import BeliefAgents, BeliefModel, belief_actions_torch  # noqa: F401
+from .local_belief import LocalBeliefAgents, local_belief_actions_torch  # noqa: F401
 from .plan import PlanAgents, plan_actions_torch  # noqa: F401
 from .forecast import ForecastAgents, forecast_torch, plan_forecast_actions_torch  # noqa: F401
 from .imitate import BCLoss, ExpertParams, ImitationLearner, LabelledRing, bc_loss_torch, distil, expert_params, get_bc_args  # noqa: F401

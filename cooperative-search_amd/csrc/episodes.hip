@@ -157,6 +157,7 @@ __global__ __launch_bounds__(256) void k_compact_small(CompactParams p) {
 #include "local.h"    // k_local_coverage_actions: the coverage baseline on n private grids under a communication range (cs_local_coverage_actions)
 #include "sweep.h"    // k_sweep_episodes: swept-area accounting of recorded episodes (cs_sweep_episodes)
 #include "belief.h"   // k_belief_actions: the target-density filter policy for moving targets (cs_belief_actions)
+#include "local_belief.h" // k_local_belief_actions: the density filter on n private grids under a communication range (cs_local_belief_actions)
 #include "plan.h"     // k_plan_actions: a receding-horizon sequence search over a base policy's grid (cs_plan_actions)
 #include "forecast.h" // k_belief_forecast, k_plan_forecast_actions: the density along the horizon and the search scored on it
 #include "label.h"    // k_label_episodes: an expert of coverage.h / belief.h relabels a recorded batch in one launch (cs_label_episodes)
@@ -449,6 +450,29 @@ int cs_belief_actions(const cs_belief_params *p, const float *state_dev, int B, 
     a.prev = prev_dev;
     a.moved = p->moved;
     hipLaunchKernelGGL(k_belief_actions, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
+    return launched(__func__);
+}
+
+int cs_local_belief_actions(const cs_local_belief_params *p, const float *state_dev, int B, int32_t *grids_dev, int32_t *prev_dev,
+                            int32_t *heard_dev, int64_t *actions_dev, void *stream) {
+    if (!p || !state_dev || !grids_dev || !prev_dev || !heard_dev || !actions_dev) return fail(__func__, "a NULL pointer");
+    const char *bad = first({B < 1 ? "B must be >= 1" : nullptr, bad_team(p->n_agents, p->side, p->view_range),
+                             bad_cover(p->keep, 16, p->lookahead, p->side), bad_width(p->state_width, p->n_agents),
+                             bad_model(p->mode, p->moved, p->sense16),
+                             p->comm_range < -1 || p->comm_range > LOC_MAX_COMM ? "comm_range must be -1 (unlimited) or 0..128" : nullptr,
+                             bad_reserved(p->reserved), misaligned({grids_dev, prev_dev, heard_dev, state_dev}, {actions_dev}),
+                             bad_steps(p->dx, p->dy)});
+    if (bad) return fail(__func__, bad);
+    // rows are cells words apart, for every agent of every env: all of them are aligned when the base is and cells % 4 == 0
+    LocalBeliefArgs a{};
+    a.b = belief_args(cover_args(state_dev, grids_dev, actions_dev, p->n_agents, p->side, p->state_width, p->view_range, p->keep, 16,
+                                 p->lookahead, grids_dev),
+                      p->mode, p->sense16, p->dx, p->dy);
+    a.b.prev = prev_dev;
+    a.b.moved = p->moved;
+    a.heard = heard_dev;
+    a.C2 = p->comm_range < 0 ? -1LL : (long long)(16 * p->comm_range) * (long long)(16 * p->comm_range);
+    hipLaunchKernelGGL(k_local_belief_actions, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
     return launched(__func__);
 }
 

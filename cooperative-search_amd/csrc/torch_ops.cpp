@@ -794,6 +794,38 @@ void belief_actions(const Tensor &state, Tensor grid, Tensor prev, Tensor action
     TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
 }
 
+// ---- the density filter under a communication range (cs_local_belief_actions): state [B, S >= 4n] float32, grids [B, n, side * side],
+// prev [B, 8, 2] and heard [B, 8] int32 (in / out), actions [B, n] int64 (out); comm_range -1 = unlimited.
+void local_belief_actions(const Tensor &state, Tensor grids, Tensor prev, Tensor heard, Tensor actions, int64_t n_agents, int64_t side,
+                          int64_t view_range, int64_t keep, int64_t lookahead, int64_t mode, int64_t moved, int64_t sense16,
+                          at::IntArrayRef dx, at::IntArrayRef dy, int64_t comm_range) {
+    const char *op = "local_belief_actions";
+    check_team(op, n_agents, side, view_range);
+    check_range(op, "keep", keep, 0, 65536);
+    check_lookahead(op, lookahead, side);
+    check_model(op, mode, sense16, moved);
+    check_steps(op, dx, dy);
+    TORCH_CHECK(comm_range >= -1 && comm_range <= 128, "coopsearch: local_belief_actions: comm_range must be -1 (unlimited) or 0..128, got ",
+                comm_range);
+    const auto [B, S] = check_rows(op, state, n_agents);
+    check_shape(op, grids, "grids", {B, n_agents, side * side});
+    check_shape(op, prev, "prev", {B, CS_MAX_AGENTS, 2});
+    check_shape(op, heard, "heard", {B, CS_MAX_AGENTS});
+    check_shape(op, actions, "actions", {B, n_agents});
+    check_lead(op, state, "state", B * S);
+    check_dev(grids, "grids", at::kInt, B * n_agents * side * side, state);
+    check_dev(prev, "prev", at::kInt, B * CS_MAX_AGENTS * 2, state);
+    check_dev(heard, "heard", at::kInt, B * CS_MAX_AGENTS, state);
+    check_dev(actions, "actions", at::kLong, B * n_agents, state);
+    cs_local_belief_params p{(int32_t)n_agents, (int32_t)side, (int32_t)view_range, (int32_t)keep, (int32_t)lookahead, (int32_t)S,
+                             (int32_t)mode, (int32_t)moved, (int32_t)sense16};   // dx, dy, comm_range, reserved: 0
+    copy_steps(p, dx, dy);
+    p.comm_range = (int32_t)comm_range;
+    const int rc = cs_local_belief_actions(&p, state.data_ptr<float>(), (int)B, grids.data_ptr<int32_t>(), prev.data_ptr<int32_t>(),
+                                           heard.data_ptr<int32_t>(), actions.data_ptr<int64_t>(), stream_of(state));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
 // ---- receding-horizon planner: state [B, S >= 4n] float32, actions, plans and scores [B, n] int64 (out), and what the segments are
 // scored on (in): grid [B, side * side] int32 for cs_plan_actions, stack [B, depth, side * side] int32 for cs_plan_forecast_actions.
 void plan_on(const char *op, bool forecast, const Tensor &state, const Tensor &levels, Tensor &actions, Tensor &plans, Tensor &scores,
@@ -1127,6 +1159,9 @@ TORCH_LIBRARY(coopsearch, m) {
           "int regrow, int lookahead, int comm_range) -> ()", &local_coverage_actions);
     m.def("belief_actions(Tensor state, Tensor(a!) grid, Tensor(b!) prev, Tensor(c!) actions, int n_agents, int side, int view_range, "
           "int keep, int lookahead, int mode, int moved, int sense16, int[] dx, int[] dy) -> ()", &belief_actions);
+    m.def("local_belief_actions(Tensor state, Tensor(a!) grids, Tensor(b!) prev, Tensor(c!) heard, Tensor(d!) actions, int n_agents, "
+          "int side, int view_range, int keep, int lookahead, int mode, int moved, int sense16, int[] dx, int[] dy, int comm_range) -> ()",
+          &local_belief_actions);
     m.def("plan_actions(Tensor state, Tensor grid, Tensor(a!) actions, Tensor(b!) plans, Tensor(c!) scores, int n_agents, int side, "
           "int view_range, int depth, int stride, int discount) -> ()", &plan_actions);
     m.def("belief_forecast(Tensor grid, Tensor pos, Tensor(a!) stack, int n_agents, int side, int mode, int sense16, int[] dx, int[] dy, "

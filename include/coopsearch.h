@@ -43,7 +43,8 @@ extern "C" {
                               cs_motion_params and cs_move_targets, then cs_belief_params and cs_belief_actions,
                               then cs_plan_params and cs_plan_actions, then cs_forecast_params, cs_belief_forecast and cs_plan_forecast_actions,
                               then cs_label_params, cs_label_episodes and cs_bc_loss, then cs_grid_params, cs_grid_features and
-                              cs_feature_episodes, then cs_local_params and cs_local_coverage_actions
+                              cs_feature_episodes, then cs_local_params and cs_local_coverage_actions, then cs_local_belief_params and
+                              cs_local_belief_actions
                               (no existing export or struct changed: a version-7 caller works unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
@@ -651,6 +652,43 @@ typedef struct cs_belief_params {
  * pointer or B < 1.  The message is cs_episodes_last_error()'s. */
 int cs_belief_actions(const cs_belief_params *p, const float *state_dev, int B, int32_t *grid_dev, int32_t *prev_dev,
                       int64_t *actions_dev, void *stream);
+
+/* ---- the density filter under a limited communication range: n private densities per env, one launch per decision (DESIGN.md
+ * section 26) ---------------------------------------------------------------------------------------------------------------
+ * cs_belief_actions keeps one density per env and predicts it with the positions of all agents.  Here agent i keeps a density of
+ * its own (cells read as clamp(cell, 0, 2^19)) and the link mask of the previous call: bit j of heard[i] says that agent i heard
+ * agent j then; it is read as (heard[i] & ((1 << n_agents) - 1)) | (1 << i).  A call PREDICTS (only if moved): agent i runs
+ * cs_belief_actions' prediction step on its own grid, its evade test seeing only the agents in heard[i], at their prev positions;
+ * it SWEEPS: agent i multiplies by keep / 65536 the cells within 16 view_range sub-units of ITS OWN current position (S_i); it
+ * MERGES: with cs_local_coverage_actions' link test on the current positions, M_i = min over the linked j of S_j, cell by cell (one
+ * hop per call; the minimum starts at 2^19 + 1), is written back; it STORES prev[i] = the quantised position and heard[i] = the
+ * mask of the agents linked to i now, for i < n_agents (slots >= n_agents of both are never touched); then the agents CHOOSE as
+ * cs_local_coverage_actions' do.  With comm_range -1 and equal grids this IS cs_belief_actions; with comm_range 0 every agent is a
+ * one-agent cs_belief_actions.  DEFINED by local_belief.local_belief_actions_torch (stock torch ops, integer after one
+ * quantisation); the kernel reproduces grids, prev, heard and actions bit for bit.
+ *   state_dev  float [B][state_width]             grids_dev  int32 [B][n_agents][side * side], in / out
+ *   prev_dev   int32 [B][8][2], in / out          heard_dev  int32 [B][8], in / out      actions_dev  int64 [B][n_agents], out */
+typedef struct cs_local_belief_params {
+    int32_t n_agents;     /* 1..8 */
+    int32_t side;         /* map_size: cells per side, 1..CS_MAX_MAP */
+    int32_t view_range;   /* sensor radius in cells, 0..CS_MAX_MAP */
+    int32_t keep;         /* rint((1 - detect_prob) * 65536), 0..65536 */
+    int32_t lookahead;    /* distance of the look-ahead point in cells, 0..side */
+    int32_t state_width;  /* floats per state row, >= 4 n_agents */
+    int32_t mode;         /* the motion model: CS_MOTION_WALK or CS_MOTION_EVADE */
+    int32_t moved;        /* 1: the targets moved since the previous call (predict first); 0: they did not */
+    int32_t sense16;      /* rint(16 sense), 0..2048 (evade only) */
+    int32_t dx[16];       /* rint(16 speed cos(2 pi k / 16)), -1024..1024 */
+    int32_t dy[16];       /* rint(16 speed sin(2 pi k / 16)), -1024..1024 */
+    int32_t comm_range;   /* communication range in whole cells, 0..128, or -1: unlimited */
+    int32_t reserved;     /* must be 0 (CS_E_CONFIG otherwise) */
+} cs_local_belief_params;
+
+/* One launch on `stream`, one workgroup per env, atomics on LDS only (integer: the result does not depend on their order), no
+ * synchronisation.  CS_E_CONFIG (before any launch) for a field out of range, a non-zero `reserved`, a NULL or misaligned
+ * pointer or B < 1.  The message is cs_episodes_last_error()'s. */
+int cs_local_belief_actions(const cs_local_belief_params *p, const float *state_dev, int B, int32_t *grids_dev, int32_t *prev_dev,
+                            int32_t *heard_dev, int64_t *actions_dev, void *stream);
 
 /* ---- receding-horizon planner over a base policy's grid, one launch per decision -------------
  * cs_coverage_actions and cs_belief_actions score three look-ahead points whose footprints overlap almost entirely: mass abeam of
