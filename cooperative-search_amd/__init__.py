@@ -31,6 +31,9 @@ from .imitate import BCLoss, ExpertParams, ImitationLearner, LabelledRing, bc_lo
 from .imitate import label_episodes, label_episodes_hip, label_episodes_torch  # noqa: F401
 from .gridobs import FeatureRing, GridAgents, GridImitationLearner, distil_grid, feature_episodes, feature_episodes_hip  # noqa: F401
 from .gridobs import feature_episodes_torch, grid_features, grid_features_hip, grid_features_torch  # noqa: F401
+from .localobs import LocalExpertParams, LocalGridAgents, distil_local_grid, local_expert_params, local_feature_episodes  # noqa: F401
+from .localobs import local_feature_episodes_hip, local_feature_episodes_torch, local_grid_features, local_grid_features_hip  # noqa: F401
+from .localobs import local_grid_features_torch, local_label_episodes  # noqa: F401
 from .render import RenderSpec, episode_tables, render_episodes, render_episodes_torch, write_frames  # noqa: F401
 
 __all__ = ["BatchedFlightEnv", "FlightSearchEnvEasy", "FlightSearchEnv", "load_targets", "default_circle_dict",

@@ -162,6 +162,7 @@ __global__ __launch_bounds__(256) void k_compact_small(CompactParams p) {
 #include "forecast.h" // k_belief_forecast, k_plan_forecast_actions: the density along the horizon and the search scored on it
 #include "label.h"    // k_label_episodes: an expert of coverage.h / belief.h relabels a recorded batch in one launch (cs_label_episodes)
 #include "gridobs.h"  // k_grid_features, k_feature_episodes: sixteen floats per agent from a policy's grid (cs_grid_features, cs_feature_episodes)
+#include "localobs.h" // k_local_grid_features, k_local_feature_episodes: the same from each agent's private grid (cs_local_grid_features, cs_local_feature_episodes)
 
 thread_local char g_eerr[160] = "";
 
@@ -546,6 +547,45 @@ int cs_feature_episodes(const cs_label_params *p, const float *s_dev, int E, int
     f.feat = feat_dev;
     f.fvec = (uintptr_t)feat_dev % 16 == 0 ? 1 : 0;
     hipLaunchKernelGGL(k_feature_episodes, dim3((unsigned)E), dim3(COV_THREADS), 0, (hipStream_t)stream, f);
+    return launched(__func__);
+}
+
+int cs_local_grid_features(const cs_grid_params *p, const float *state_dev, int B, const int32_t *grids_dev, float *feat_dev,
+                           void *stream) {
+    if (!p || !state_dev || !grids_dev || !feat_dev) return fail(__func__, "a NULL pointer");
+    const char *bad = first({B < 1 ? "B must be >= 1" : nullptr, bad_team(p->n_agents, p->side, p->view_range),
+                             bad_cover(0, 1, p->lookahead, p->side), bad_width(p->state_width, p->n_agents), bad_reserved(p->reserved),
+                             misaligned({grids_dev, state_dev, feat_dev}, {})});
+    if (bad) return fail(__func__, bad);
+    const LocalGridObsArgs a{state_dev, grids_dev, feat_dev, p->n_agents, p->side, p->state_width, 16 * p->view_range, 16 * p->lookahead};
+    hipLaunchKernelGGL(k_local_grid_features, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
+    return launched(__func__);
+}
+
+int cs_local_feature_episodes(const cs_local_label_params *p, const float *s_dev, const int32_t *lens_dev, int E, int T, float *feat_dev,
+                              int64_t *labels_dev, int32_t *grids_dev, int32_t *prev_dev, int32_t *heard_dev, void *stream) {
+    if (!p || !s_dev || !lens_dev || !feat_dev || !grids_dev) return fail(__func__, "a NULL pointer");
+    cs_label_params q{p->expert, p->n_agents, p->side, p->view_range, p->keep, p->regrow,
+                      p->lookahead, p->state_width, p->mode, p->sense16, p->every, p->moving};   // cs_label_params' fields: one ladder
+    for (int k = 0; k < 16; k++) {
+        q.dx[k] = p->dx[k];
+        q.dy[k] = p->dy[k];
+    }
+    q.reserved = p->reserved;
+    const char *bad = first({bad_label(&q, E, T, prev_dev, "prev_dev is the belief filter's (the coverage filter keeps no positions)",
+                                       {s_dev, lens_dev, feat_dev, grids_dev, prev_dev, heard_dev}, {labels_dev}),
+                             p->comm_range < -1 || p->comm_range > LOC_MAX_COMM ? "comm_range must be -1 (unlimited) or 0..128" : nullptr,
+                             p->expert == LABEL_COVERAGE && heard_dev ? "heard_dev is the belief filter's (the coverage filter keeps no masks)"
+                                                                     : nullptr});
+    if (bad) return fail(__func__, bad);
+    // rows of the workspace are cells words apart, for every agent of every episode: all are aligned when the base is and cells % 4 == 0
+    LocalFeatArgs f{};
+    f.l = label_args(&q, s_dev, T, lens_dev, labels_dev, grids_dev, prev_dev);
+    f.feat = feat_dev;
+    f.heard_out = heard_dev;
+    f.C2 = p->comm_range < 0 ? -1LL : (long long)(16 * p->comm_range) * (long long)(16 * p->comm_range);
+    f.fvec = (uintptr_t)feat_dev % 16 == 0 ? 1 : 0;
+    hipLaunchKernelGGL(k_local_feature_episodes, dim3((unsigned)E), dim3(COV_THREADS), 0, (hipStream_t)stream, f);
     return launched(__func__);
 }
 

@@ -1099,6 +1099,76 @@ void feature_episodes(const Tensor &s, const Tensor &lens, Tensor feat, c10::opt
              prev_out, expert, n_agents, side, view_range, keep, regrow, lookahead, mode, sense16, every, moving, dx, dy);
 }
 
+// ---- grid observations of private grids, one decision (cs_local_grid_features): state [B, S >= 4n] float32 and grids [B, n, side *
+// side] int32 (in, read only), feat [B, n, 16] float32 (out).
+void local_grid_features(const Tensor &state, const Tensor &grids, Tensor feat, int64_t n_agents, int64_t side, int64_t view_range,
+                         int64_t lookahead) {
+    const char *op = "local_grid_features";
+    check_team(op, n_agents, side, view_range);
+    check_lookahead(op, lookahead, side);
+    const auto [B, S] = check_rows(op, state, n_agents);
+    check_shape(op, grids, "grids", {B, n_agents, side * side});
+    check_shape(op, feat, "feat", {B, n_agents, 16});
+    check_lead(op, state, "state", B * S);
+    check_dev(grids, "grids", at::kInt, B * n_agents * side * side, state);
+    check_f32(feat, "feat", B * n_agents * 16, state);
+    const cs_grid_params p{(int32_t)n_agents, (int32_t)side, (int32_t)view_range, (int32_t)lookahead, (int32_t)S, 0};
+    const int rc = cs_local_grid_features(&p, state.data_ptr<float>(), (int)B, grids.data_ptr<int32_t>(), feat.data_ptr<float>(),
+                                          stream_of(state));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
+// ---- a local filter over recorded episodes (cs_local_feature_episodes): s [E, T, S >= 4n] float32 and lens [E] int32 (in); feat [E, T,
+// n, 16] float32 and grids [E, n, side * side] int32 (out, required: grids is the kernel's workspace); labels [E, T, n] int64, prev_out
+// [E, 8, 2] and heard_out [E, 8] int32 (out, optional; the last two are the belief filter's).
+void local_feature_episodes(const Tensor &s, const Tensor &lens, Tensor feat, c10::optional<Tensor> labels, Tensor grids,
+                            c10::optional<Tensor> prev_out, c10::optional<Tensor> heard_out, int64_t expert, int64_t n_agents, int64_t side,
+                            int64_t view_range, int64_t keep, int64_t regrow, int64_t lookahead, int64_t mode, int64_t sense16, int64_t every,
+                            int64_t moving, at::IntArrayRef dx, at::IntArrayRef dy, int64_t comm_range) {
+    const char *op = "local_feature_episodes";
+    TORCH_CHECK(expert == 0 || expert == 1, "coopsearch: ", op, ": expert must be 0 (coverage) or 1 (belief), got ", expert);
+    check_team(op, n_agents, side, view_range);
+    check_range(op, "keep", keep, 0, 65536);
+    check_range(op, "regrow", regrow, 1, 16);
+    check_lookahead(op, lookahead, side);
+    check_model(op, mode, sense16);
+    TORCH_CHECK(every >= 1 && every <= INT32_MAX, "coopsearch: ", op, ": every must be >= 1, got ", every);
+    check_flag(op, "moving", moving);
+    check_steps(op, dx, dy);
+    TORCH_CHECK(comm_range >= -1 && comm_range <= 128, "coopsearch: ", op, ": comm_range must be -1 (unlimited) or 0..128, got ", comm_range);
+    TORCH_CHECK(s.dim() == 3 && s.size(0) >= 1 && s.size(0) <= INT32_MAX && s.size(1) >= 1 && s.size(1) <= INT32_MAX &&
+                    s.size(2) >= 4 * n_agents && s.size(2) <= INT32_MAX,
+                "coopsearch: ", op, ": s must be [E, T, S] with E >= 1, T >= 1 and S >= 4 n_agents = ", 4 * n_agents);
+    const int64_t E = s.size(0), T = s.size(1), S = s.size(2);
+    check_shape(op, lens, "lens", {E});
+    check_shape(op, feat, "feat", {E, T, n_agents, 16});
+    if (has(labels)) check_shape(op, *labels, "labels", {E, T, n_agents});
+    check_shape(op, grids, "grids", {E, n_agents, side * side});
+    if (has(prev_out)) {
+        TORCH_CHECK(expert == 1, "coopsearch: ", op, ": prev_out is the belief filter's (the coverage filter keeps no positions)");
+        check_shape(op, *prev_out, "prev_out", {E, CS_MAX_AGENTS, 2});
+    }
+    if (has(heard_out)) {
+        TORCH_CHECK(expert == 1, "coopsearch: ", op, ": heard_out is the belief filter's (the coverage filter keeps no masks)");
+        check_shape(op, *heard_out, "heard_out", {E, CS_MAX_AGENTS});
+    }
+    check_lead(op, s, "s", E * T * S);
+    check_dev(lens, "lens", at::kInt, E, s);
+    check_f32(feat, "feat", E * T * n_agents * 16, s);
+    if (has(labels)) check_dev(*labels, "labels", at::kLong, E * T * n_agents, s);
+    check_dev(grids, "grids", at::kInt, E * n_agents * side * side, s);
+    if (has(prev_out)) check_dev(*prev_out, "prev_out", at::kInt, E * CS_MAX_AGENTS * 2, s);
+    if (has(heard_out)) check_dev(*heard_out, "heard_out", at::kInt, E * CS_MAX_AGENTS, s);
+    cs_local_label_params p{(int32_t)expert, (int32_t)n_agents, (int32_t)side, (int32_t)view_range, (int32_t)keep, (int32_t)regrow,
+                            (int32_t)lookahead, (int32_t)S, (int32_t)mode, (int32_t)sense16, (int32_t)every, (int32_t)moving};   // the rest: 0
+    copy_steps(p, dx, dy);
+    p.comm_range = (int32_t)comm_range;
+    const int rc = cs_local_feature_episodes(&p, s.data_ptr<float>(), lens.data_ptr<int32_t>(), (int)E, (int)T, feat.data_ptr<float>(),
+                                             opt_ptr<int64_t>(labels), grids.data_ptr<int32_t>(), opt_ptr<int32_t>(prev_out),
+                                             opt_ptr<int32_t>(heard_out), stream_of(s));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
 }  // namespace
 
 TORCH_LIBRARY(coopsearch, m) {
@@ -1193,4 +1263,9 @@ TORCH_LIBRARY(coopsearch, m) {
     m.def("feature_episodes(Tensor s, Tensor lens, Tensor(a!) feat, Tensor(b!)? labels, Tensor(c!)? grid_out, Tensor(d!)? prev_out, "
           "int expert, int n_agents, int side, int view_range, int keep, int regrow, int lookahead, int mode, int sense16, int every, "
           "int moving, int[] dx, int[] dy) -> ()", &feature_episodes);
+    m.def("local_grid_features(Tensor state, Tensor grids, Tensor(a!) feat, int n_agents, int side, int view_range, int lookahead) -> ()",
+          &local_grid_features);
+    m.def("local_feature_episodes(Tensor s, Tensor lens, Tensor(a!) feat, Tensor(b!)? labels, Tensor(c!) grids, Tensor(d!)? prev_out, "
+          "Tensor(e!)? heard_out, int expert, int n_agents, int side, int view_range, int keep, int regrow, int lookahead, int mode, "
+          "int sense16, int every, int moving, int[] dx, int[] dy, int comm_range) -> ()", &local_feature_episodes);
 }

@@ -44,7 +44,7 @@ extern "C" {
                               then cs_plan_params and cs_plan_actions, then cs_forecast_params, cs_belief_forecast and cs_plan_forecast_actions,
                               then cs_label_params, cs_label_episodes and cs_bc_loss, then cs_grid_params, cs_grid_features and
                               cs_feature_episodes, then cs_local_params and cs_local_coverage_actions, then cs_local_belief_params and
-                              cs_local_belief_actions
+                              cs_local_belief_actions, then cs_local_label_params, cs_local_grid_features and cs_local_feature_episodes
                               (no existing export or struct changed: a version-7 caller works unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
@@ -819,6 +819,54 @@ typedef struct cs_grid_params {
 int cs_grid_features(const cs_grid_params *p, const float *state_dev, int B, const int32_t *grid_dev, float *feat_dev, void *stream);
 int cs_feature_episodes(const cs_label_params *p, const float *s_dev, int E, int T, const int32_t *lens_dev, float *feat_dev,
                         int64_t *labels_dev, int32_t *grid_out_dev, int32_t *prev_out_dev, void *stream);
+
+/* ---- grid observations of PRIVATE grids: sixteen floats per agent from its own grid under a communication range (DESIGN.md
+ * section 27) ------------------------------------------------------------------------------------------------------------------
+ * cs_grid_features reads the one grid of an env for every agent.  cs_local_coverage_actions and cs_local_belief_actions keep one
+ * grid per AGENT; here agent i's sixteen probes (the same probe points, sums, shift and scale) read grids[b][i] alone.
+ * DEFINED by localobs.local_grid_features_torch and localobs.local_feature_episodes_torch (stock torch ops, integer after one
+ * quantisation); the kernels reproduce them bit for bit.
+ *   cs_local_grid_features     per decision, on the grids cs_local_coverage_actions or cs_local_belief_actions left after its call
+ *     on the same state:
+ *     state_dev  float [B][state_width], in     grids_dev  int32 [B][n_agents][side * side], in (READ ONLY)
+ *     feat_dev   float [B][n_agents][16], out
+ *   cs_local_feature_episodes  for a recorded batch: row t of a coverage filter (expert 0) is cs_local_coverage_actions, row t of a
+ *     belief filter (expert 1) is cs_local_belief_actions with moved = (moving && t > 0 && (t - 1) % every == 0), from n fresh grids
+ *     (65536 everywhere, stored positions and link masks 0), followed by cs_local_grid_features on the grids as the row left them.
+ *     Only the rows t < lens[e] are walked (lens[e] is read clamped to 0..T).
+ *     s_dev, lens_dev  as cs_label_episodes'     feat_dev  float [E][T][n_agents][16], out (rows t >= lens[e]: 0)
+ *     labels_dev  int64 [E][T][n_agents], out (rows t >= lens[e]: 0), or NULL: the choose step is skipped altogether
+ *     grids_dev   int32 [E][n_agents][side * side], REQUIRED: the kernel's workspace (it fills it itself; the content on entry does
+ *                 not matter), and on return every agent's grid after the episode's last live row
+ *     prev_dev    int32 [E][8][2], out, or NULL; heard_dev  int32 [E][8], out, or NULL; both belief only (slots >= n_agents: 0) */
+typedef struct cs_local_label_params {
+    int32_t expert;       /* 0: cs_local_coverage_actions' policy, 1: cs_local_belief_actions' */
+    int32_t n_agents;     /* 1..8 */
+    int32_t side;         /* map_size: cells per side, 1..CS_MAX_MAP */
+    int32_t view_range;   /* sensor radius in cells, 0..CS_MAX_MAP */
+    int32_t keep;         /* rint((1 - detect_prob) * 65536), 0..65536 */
+    int32_t regrow;       /* regrowth shift, 1..16 (coverage; checked, then unused, for belief) */
+    int32_t lookahead;    /* distance of the look-ahead point and of the inner probe ring in cells, 0..side */
+    int32_t state_width;  /* floats per state row, >= 4 n_agents */
+    int32_t mode;         /* belief: the motion model, CS_MOTION_WALK or CS_MOTION_EVADE */
+    int32_t sense16;      /* belief: rint(16 sense), 0..2048 (evade only) */
+    int32_t every;        /* belief: env steps between two moves of the targets, >= 1 */
+    int32_t moving;       /* belief: 1 if the targets move at all (speed > 0), else 0 */
+    int32_t dx[16];       /* belief: rint(16 speed cos(2 pi k / 16)), -1024..1024 */
+    int32_t dy[16];       /* belief: rint(16 speed sin(2 pi k / 16)), -1024..1024 */
+    int32_t comm_range;   /* communication range in whole cells, 0..128, or -1: unlimited */
+    int32_t reserved;     /* must be 0 (CS_E_CONFIG otherwise) */
+} cs_local_label_params;
+
+/* One launch each on `stream`, one workgroup per env / per episode, no global atomics (cs_local_feature_episodes: LDS atomics as
+ * cs_local_belief_actions), no synchronisation.  CS_E_CONFIG (before any launch) for a field out of range (expert included), a
+ * non-zero `reserved`, a NULL or misaligned required pointer (labels_dev, prev_dev and heard_dev may be NULL; prev_dev and heard_dev
+ * must be NULL for the coverage filter), B < 1, E < 1 or T < 1.  Both decide their 16-byte paths themselves.  The message is
+ * cs_episodes_last_error()'s. */
+int cs_local_grid_features(const cs_grid_params *p, const float *state_dev, int B, const int32_t *grids_dev, float *feat_dev,
+                           void *stream);
+int cs_local_feature_episodes(const cs_local_label_params *p, const float *s_dev, const int32_t *lens_dev, int E, int T, float *feat_dev,
+                              int64_t *labels_dev, int32_t *grids_dev, int32_t *prev_dev, int32_t *heard_dev, void *stream);
 
 /* ---- QMIX learner: the GRU recurrence of the agent network over T steps, forward and backward ---------------------
  * Replaces the per-transition unroll of policy/qmix.py:160-182 (get_q_values) over network/base_net.py:40-46
