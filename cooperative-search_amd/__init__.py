@@ -26,6 +26,7 @@ from .motion import TargetMotion, MovingTargetEnv, move_targets_torch, make_env 
 from .belief import BeliefAgents, BeliefModel, belief_actions_torch  # noqa: F401
 from .local_belief import LocalBeliefAgents, local_belief_actions_torch  # noqa: F401
 from .plan import PlanAgents, plan_actions_torch  # noqa: F401
+from .local_plan import LocalPlanAgents, local_plan_actions_torch  # noqa: F401
 from .forecast import ForecastAgents, forecast_torch, plan_forecast_actions_torch  # noqa: F401
 from .imitate import BCLoss, ExpertParams, ImitationLearner, LabelledRing, bc_loss_torch, distil, expert_params, get_bc_args  # noqa: F401
 from .imitate import label_episodes, label_episodes_hip, label_episodes_torch  # noqa: F401

@@ -159,6 +159,7 @@ __global__ __launch_bounds__(256) void k_compact_small(CompactParams p) {
 #include "belief.h"   // k_belief_actions: the target-density filter policy for moving targets (cs_belief_actions)
 #include "local_belief.h" // k_local_belief_actions: the density filter on n private grids under a communication range (cs_local_belief_actions)
 #include "plan.h"     // k_plan_actions: a receding-horizon sequence search over a base policy's grid (cs_plan_actions)
+#include "local_plan.h" // k_local_plan_actions: the sequence search on n private grids under a communication range (cs_local_plan_actions)
 #include "forecast.h" // k_belief_forecast, k_plan_forecast_actions: the density along the horizon and the search scored on it
 #include "label.h"    // k_label_episodes: an expert of coverage.h / belief.h relabels a recorded batch in one launch (cs_label_episodes)
 #include "gridobs.h"  // k_grid_features, k_feature_episodes: sixteen floats per agent from a policy's grid (cs_grid_features, cs_feature_episodes)
@@ -480,6 +481,25 @@ int cs_local_belief_actions(const cs_local_belief_params *p, const float *state_
 int cs_plan_actions(const cs_plan_params *p, const float *state_dev, int B, const int32_t *grid_dev, int64_t *actions_dev,
                     int64_t *plans_dev, int64_t *scores_dev, void *stream) {
     return plan_launch(__func__, false, p, state_dev, B, grid_dev, actions_dev, plans_dev, scores_dev, stream);
+}
+
+int cs_local_plan_actions(const cs_local_plan_params *p, const float *state_dev, int B, const int32_t *grids_dev, int64_t *actions_dev,
+                          int64_t *plans_dev, int64_t *scores_dev, void *stream) {
+    if (!p || !state_dev || !grids_dev || !actions_dev || !plans_dev || !scores_dev) return fail(__func__, "a NULL pointer");
+    const char *bad = first({B < 1 ? "B must be >= 1" : nullptr, bad_team(p->n_agents, p->side, p->view_range),
+                             bad_plan(p->depth, p->stride, p->discount), bad_width(p->state_width, p->n_agents),
+                             p->comm_range < -1 || p->comm_range > LOC_MAX_COMM ? "comm_range must be -1 (unlimited) or 0..128" : nullptr,
+                             bad_reserved(p->reserved), misaligned({grids_dev, state_dev}, {actions_dev, plans_dev, scores_dev})});
+    if (bad) return fail(__func__, bad);
+    const int cells = p->side * p->side;
+    int seqs = 1;
+    for (int d = 0; d < p->depth; d++) seqs *= 3;
+    // rows are cells words apart, for every agent of every env: all of them are aligned when the base is and cells % 4 == 0
+    const LocalPlanArgs a{PlanArgs{state_dev, grids_dev, actions_dev, plans_dev, scores_dev, p->n_agents, p->side, p->state_width,
+                                   16 * p->view_range, p->depth, p->stride, p->discount, (3 * seqs - 3) / 2, seqs, vec4_ok(cells, grids_dev)},
+                          p->comm_range < 0 ? -1LL : (long long)(16 * p->comm_range) * (long long)(16 * p->comm_range)};
+    hipLaunchKernelGGL(k_local_plan_actions, dim3((unsigned)B), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
+    return launched(__func__);
 }
 
 int cs_belief_forecast(const cs_forecast_params *p, const int32_t *grid_dev, const int32_t *pos_dev, int B, int32_t *stack_dev,

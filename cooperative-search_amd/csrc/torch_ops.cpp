@@ -866,6 +866,34 @@ void plan_forecast_actions(const Tensor &state, const Tensor &stack, Tensor acti
     plan_on("plan_forecast_actions", true, state, stack, actions, plans, scores, n_agents, side, view_range, depth, stride, discount);
 }
 
+// ---- the planner on private grids under a communication range (cs_local_plan_actions): state [B, S >= 4n] float32, grids [B, n,
+// side * side] int32 (in), actions, plans and scores [B, n] int64 (out); comm_range -1 = unlimited.
+void local_plan_actions(const Tensor &state, const Tensor &grids, Tensor actions, Tensor plans, Tensor scores, int64_t n_agents,
+                        int64_t side, int64_t view_range, int64_t depth, int64_t stride, int64_t discount, int64_t comm_range) {
+    const char *op = "local_plan_actions";
+    check_team(op, n_agents, side, view_range);
+    check_range(op, "depth", depth, 1, 5);
+    check_range(op, "stride", stride, 1, 8);
+    check_range(op, "discount", discount, 0, 256);
+    TORCH_CHECK(comm_range >= -1 && comm_range <= 128, "coopsearch: local_plan_actions: comm_range must be -1 (unlimited) or 0..128, got ",
+                comm_range);
+    const auto [B, S] = check_rows(op, state, n_agents);
+    check_shape(op, grids, "grids", {B, n_agents, side * side});
+    check_shape(op, actions, "actions", {B, n_agents});
+    check_shape(op, plans, "plans", {B, n_agents});
+    check_shape(op, scores, "scores", {B, n_agents});
+    check_lead(op, state, "state", B * S);
+    check_dev(grids, "grids", at::kInt, B * n_agents * side * side, state);
+    check_dev(actions, "actions", at::kLong, B * n_agents, state);
+    check_dev(plans, "plans", at::kLong, B * n_agents, state);
+    check_dev(scores, "scores", at::kLong, B * n_agents, state);
+    const cs_local_plan_params p{(int32_t)n_agents, (int32_t)side, (int32_t)view_range, (int32_t)depth, (int32_t)stride, (int32_t)discount,
+                                 (int32_t)S, (int32_t)comm_range, 0};
+    const int rc = cs_local_plan_actions(&p, state.data_ptr<float>(), (int)B, grids.data_ptr<int32_t>(), actions.data_ptr<int64_t>(),
+                                         plans.data_ptr<int64_t>(), scores.data_ptr<int64_t>(), stream_of(state));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
 // ---- the density along the planning horizon (cs_belief_forecast): grid [B, side * side] int32 (in), pos [B, 8, 2] int32 (in),
 // stack [B, L, side * side] int32 (out), L = moves.size().
 void belief_forecast(const Tensor &grid, const Tensor &pos, Tensor stack, int64_t n_agents, int64_t side, int64_t mode, int64_t sense16,
@@ -1234,6 +1262,8 @@ TORCH_LIBRARY(coopsearch, m) {
           &local_belief_actions);
     m.def("plan_actions(Tensor state, Tensor grid, Tensor(a!) actions, Tensor(b!) plans, Tensor(c!) scores, int n_agents, int side, "
           "int view_range, int depth, int stride, int discount) -> ()", &plan_actions);
+    m.def("local_plan_actions(Tensor state, Tensor grids, Tensor(a!) actions, Tensor(b!) plans, Tensor(c!) scores, int n_agents, int side, "
+          "int view_range, int depth, int stride, int discount, int comm_range) -> ()", &local_plan_actions);
     m.def("belief_forecast(Tensor grid, Tensor pos, Tensor(a!) stack, int n_agents, int side, int mode, int sense16, int[] dx, int[] dy, "
           "int[] moves) -> ()", &belief_forecast);
     m.def("plan_forecast_actions(Tensor state, Tensor stack, Tensor(a!) actions, Tensor(b!) plans, Tensor(c!) scores, int n_agents, "

@@ -57,6 +57,23 @@ def weights(depth, discount):
     return w
 
 
+def sequence_points(X, Y, h, plans, side, depth, stride):
+    """The segment end points of one sequence per row: quantised poses X, Y, h and sequence indices `plans`, int64 [B] each ->
+    (px, py) int64 [B, depth], P_0 .. P_{D-1} of the module docstring (local_plan.py claims the discs around them)."""
+    sx, sy = (torch.tensor(t, dtype=torch.int64, device=X.device) for t in step_tables())
+    turn = torch.tensor(TURN, dtype=torch.int64, device=X.device)
+    lim, px, py = 16 * side, [], []
+    for d in range(depth):
+        t = turn[(plans // 3 ** (depth - 1 - d)) % 3]
+        for _ in range(stride):
+            h = (h + t) % bl.HEADINGS
+            X = torch.clamp(X + sx[h], 0, lim)
+            Y = torch.clamp(Y + sy[h], 0, lim)
+        px.append(X)
+        py.append(Y)
+    return torch.stack(px, 1), torch.stack(py, 1)
+
+
 def _check_params(n, side, view_range, depth, stride, discount):
     bl._check_team("plan", n, side, view_range)
     if not 1 <= depth <= MAX_DEPTH or not 1 <= stride <= MAX_STRIDE or not 0 <= discount <= 256:

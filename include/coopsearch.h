@@ -44,7 +44,8 @@ extern "C" {
                               then cs_plan_params and cs_plan_actions, then cs_forecast_params, cs_belief_forecast and cs_plan_forecast_actions,
                               then cs_label_params, cs_label_episodes and cs_bc_loss, then cs_grid_params, cs_grid_features and
                               cs_feature_episodes, then cs_local_params and cs_local_coverage_actions, then cs_local_belief_params and
-                              cs_local_belief_actions, then cs_local_label_params, cs_local_grid_features and cs_local_feature_episodes
+                              cs_local_belief_actions, then cs_local_label_params, cs_local_grid_features and cs_local_feature_episodes,
+                              then cs_local_plan_params and cs_local_plan_actions
                               (no existing export or struct changed: a version-7 caller works unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
@@ -867,6 +868,35 @@ int cs_local_grid_features(const cs_grid_params *p, const float *state_dev, int 
                            void *stream);
 int cs_local_feature_episodes(const cs_local_label_params *p, const float *s_dev, const int32_t *lens_dev, int E, int T, float *feat_dev,
                               int64_t *labels_dev, int32_t *grids_dev, int32_t *prev_dev, int32_t *heard_dev, void *stream);
+
+/* ---- the receding-horizon planner on PRIVATE grids under a communication range, one launch per decision ----
+ * cs_plan_actions reads one grid per env and lets every agent see every earlier agent's claim.  Here agent i plans on its own grid,
+ * grids[b][i] (what cs_local_coverage_actions or cs_local_belief_actions left; READ ONLY, every cell as clamp(cell, 0, 2^19)), less
+ * the discs of the winning sequences of the agents j < i that it is linked to: cs_local_coverage_actions' link test on the current
+ * positions (i == j, or comm_range < 0, or (X_i - X_j)^2 + (Y_i - Y_j)^2 < (16 comm_range)^2 in sub-units; strict, 64-bit).  The
+ * sequences, their end points, the gains less the ancestors' discs, the weights, the score, the tie rule and the action are
+ * cs_plan_actions'.  With comm_range -1 and equal grids this IS cs_plan_actions; with comm_range 0 every agent is a one-agent
+ * cs_plan_actions on its own grid.  DEFINED by local_plan.local_plan_actions_torch (stock torch ops, integer after one
+ * quantisation); the kernel reproduces actions, plans and scores bit for bit.
+ *   state_dev  float [B][state_width]       grids_dev  int32 [B][n_agents][side * side], in
+ *   actions_dev, plans_dev, scores_dev  int64 [B][n_agents], out, as cs_plan_actions' */
+typedef struct cs_local_plan_params {
+    int32_t n_agents;     /* 1..8 */
+    int32_t side;         /* map_size: cells per side, 1..CS_MAX_MAP */
+    int32_t view_range;   /* sensor radius in cells, 0..CS_MAX_MAP */
+    int32_t depth;        /* segments per sequence, 1..5 */
+    int32_t stride;       /* env steps per segment, 1..8 */
+    int32_t discount;     /* Q8 weight ratio of successive segments, 0..256 */
+    int32_t state_width;  /* floats per state row, >= 4 n_agents */
+    int32_t comm_range;   /* communication range in whole cells, 0..128, or -1: unlimited */
+    int32_t reserved;     /* must be 0 (CS_E_CONFIG otherwise) */
+} cs_local_plan_params;
+
+/* One launch on `stream`, one workgroup per env, no atomics, no synchronisation.  CS_E_CONFIG (before any launch) for a field out
+ * of range, a non-zero `reserved`, a NULL or misaligned pointer or B < 1.  It decides its 16-byte path itself.  The message is
+ * cs_episodes_last_error()'s. */
+int cs_local_plan_actions(const cs_local_plan_params *p, const float *state_dev, int B, const int32_t *grids_dev, int64_t *actions_dev,
+                          int64_t *plans_dev, int64_t *scores_dev, void *stream);
 
 /* ---- QMIX learner: the GRU recurrence of the agent network over T steps, forward and backward ---------------------
  * Replaces the per-transition unroll of policy/qmix.py:160-182 (get_q_values) over network/base_net.py:40-46
