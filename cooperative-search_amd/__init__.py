@@ -28,6 +28,7 @@ from .local_belief import LocalBeliefAgents, local_belief_actions_torch  # noqa:
 from .plan import PlanAgents, plan_actions_torch  # noqa: F401
 from .local_plan import LocalPlanAgents, local_plan_actions_torch  # noqa: F401
 from .forecast import ForecastAgents, forecast_torch, plan_forecast_actions_torch  # noqa: F401
+from .local_forecast import LocalForecastAgents, local_forecast_torch, local_plan_forecast_actions_torch  # noqa: F401
 from .imitate import BCLoss, ExpertParams, ImitationLearner, LabelledRing, bc_loss_torch, distil, expert_params, get_bc_args  # noqa: F401
 from .imitate import label_episodes, label_episodes_hip, label_episodes_torch  # noqa: F401
 from .gridobs import FeatureRing, GridAgents, GridImitationLearner, distil_grid, feature_episodes, feature_episodes_hip  # noqa: F401

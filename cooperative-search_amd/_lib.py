@@ -21,7 +21,7 @@ FREEZE_DONE, AUTO_RESET, ACTIONS_I64, KERNEL_GROUP, KERNEL_LANE, KERNEL_SOLO, KE
 
 EXPORTS = ["cs_abi_version", "cs_source_hash", "cs_has_legacy_kernels", "cs_last_error", "cs_state_layout", "cs_init", "cs_seed", "cs_reset", "cs_step",
            "cs_rollout", "cs_rollout_policy", "cs_rollout_policy_flight", "cs_collect_flight", "cs_emit", "cs_snapshot_bytes", "cs_snapshot", "cs_restore", "cs_metrics", "cs_mt_canonical", "cs_mt_advance", "cs_policy_packed_floats", "cs_policy_pack", "cs_policy_pack_device", "cs_policy_forward",
-           "cs_policy_conv_features", "cs_policy_conv_features_backward_scratch", "cs_policy_conv_features_backward", "cs_policy_last_error", "cs_store_episodes", "cs_store_episodes_compact", "cs_render_episodes", "cs_coverage_actions", "cs_sweep_episodes", "cs_move_targets", "cs_belief_actions", "cs_plan_actions", "cs_belief_forecast", "cs_plan_forecast_actions", "cs_label_episodes", "cs_grid_features", "cs_feature_episodes", "cs_local_coverage_actions", "cs_local_belief_actions", "cs_local_grid_features", "cs_local_feature_episodes", "cs_local_plan_actions", "cs_episodes_last_error", "cs_epsilon_step",
+           "cs_policy_conv_features", "cs_policy_conv_features_backward_scratch", "cs_policy_conv_features_backward", "cs_policy_last_error", "cs_store_episodes", "cs_store_episodes_compact", "cs_render_episodes", "cs_coverage_actions", "cs_sweep_episodes", "cs_move_targets", "cs_belief_actions", "cs_plan_actions", "cs_belief_forecast", "cs_plan_forecast_actions", "cs_label_episodes", "cs_grid_features", "cs_feature_episodes", "cs_local_coverage_actions", "cs_local_belief_actions", "cs_local_grid_features", "cs_local_feature_episodes", "cs_local_plan_actions", "cs_local_belief_forecast", "cs_local_plan_forecast_actions", "cs_episodes_last_error", "cs_epsilon_step",
            "cs_gru_seq_forward", "cs_gru_seq_backward", "cs_episode_returns", "cs_gae", "cs_ppo_loss", "cs_bc_loss", "cs_learn_last_error"]
 
 
@@ -214,6 +214,8 @@ def load():
     L.cs_local_grid_features.argtypes = [C.POINTER(CsGridParams), vp, C.c_int, vp, vp, vp]
     L.cs_local_feature_episodes.argtypes = [C.POINTER(CsLocalLabelParams), vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     L.cs_local_plan_actions.argtypes = [C.POINTER(CsLocalPlanParams), vp, C.c_int, vp, vp, vp, vp, vp]
+    L.cs_local_belief_forecast.argtypes = [C.POINTER(CsForecastParams), vp, vp, vp, C.c_int, vp, vp]
+    L.cs_local_plan_forecast_actions.argtypes = [C.POINTER(CsLocalPlanParams), vp, C.c_int, vp, vp, vp, vp, vp]
     L.cs_bc_loss.argtypes = [vp] * 4 + [C.c_int64, C.c_int, C.c_int] + [vp] * 4 + [C.c_int64, vp]
     L.cs_policy_pack.argtypes = [vp] * 10 + [C.c_int, C.c_int, vp]
     L.cs_policy_pack_device.argtypes = [vp] * 10 + [C.c_int, C.c_int, vp, vp, vp]

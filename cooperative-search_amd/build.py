@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("COOPSEARCH_LIB") or os.path.join(CSRC, "libcoopsearch
 # torch.ops.coopsearch.*: the op layer over the C ABI (override: the sanitizer build of tests/test_sanitizers_cpu.py)
 TORCH_LIB_PATH = os.environ.get("COOPSEARCH_TORCH_LIB") or os.path.join(CSRC, "coopsearch_torch.so")
 SOURCES = ["coopsearch.hip", "rollout_policy.h", "rollout_lane.h", "rollout_oct.h", "rollout_od.h", "rollout_lanev.h",
-           "flight_map.h", "snapshot.h", "policy.hip", "episodes.hip", "render.h", "coverage.h", "local.h", "sweep.h", "motion.h", "belief.h", "local_belief.h", "plan.h", "local_plan.h", "forecast.h", "label.h", "gridobs.h", "localobs.h", "policy_dev.h", "conv_bwd.h", "gru_seq.h", "returns.h", "ppo.h", "bc_loss.h", "trig_table.inc"]
+           "flight_map.h", "snapshot.h", "policy.hip", "episodes.hip", "render.h", "coverage.h", "local.h", "sweep.h", "motion.h", "belief.h", "local_belief.h", "plan.h", "local_plan.h", "forecast.h", "local_forecast.h", "label.h", "gridobs.h", "localobs.h", "policy_dev.h", "conv_bwd.h", "gru_seq.h", "returns.h", "ppo.h", "bc_loss.h", "trig_table.inc"]
 HEADERS = [os.path.join(ROOT, "include", "coopsearch.h")]
 
 

@@ -161,6 +161,7 @@ __global__ __launch_bounds__(256) void k_compact_small(CompactParams p) {
 #include "plan.h"     // k_plan_actions: a receding-horizon sequence search over a base policy's grid (cs_plan_actions)
 #include "local_plan.h" // k_local_plan_actions: the sequence search on n private grids under a communication range (cs_local_plan_actions)
 #include "forecast.h" // k_belief_forecast, k_plan_forecast_actions: the density along the horizon and the search scored on it
+#include "local_forecast.h" // k_local_belief_forecast, k_local_plan_forecast_actions: the same on n private grids under a communication range
 #include "label.h"    // k_label_episodes: an expert of coverage.h / belief.h relabels a recorded batch in one launch (cs_label_episodes)
 #include "gridobs.h"  // k_grid_features, k_feature_episodes: sixteen floats per agent from a policy's grid (cs_grid_features, cs_feature_episodes)
 #include "localobs.h" // k_local_grid_features, k_local_feature_episodes: the same from each agent's private grid (cs_local_grid_features, cs_local_feature_episodes)
@@ -532,6 +533,63 @@ int cs_belief_forecast(const cs_forecast_params *p, const int32_t *grid_dev, con
 int cs_plan_forecast_actions(const cs_plan_params *p, const float *state_dev, int B, const int32_t *stack_dev, int64_t *actions_dev,
                              int64_t *plans_dev, int64_t *scores_dev, void *stream) {
     return plan_launch(__func__, true, p, state_dev, B, stack_dev, actions_dev, plans_dev, scores_dev, stream);
+}
+
+int cs_local_belief_forecast(const cs_forecast_params *p, const int32_t *grids_dev, const int32_t *prev_dev, const int32_t *heard_dev,
+                             int B, int32_t *stacks_dev, void *stream) {
+    if (!p || !grids_dev || !prev_dev || !heard_dev || !stacks_dev) return fail(__func__, "a NULL pointer");
+    const char *bad = first({B < 1 ? "B must be >= 1" : nullptr, bad_team(p->n_agents, p->side, 0),
+                             p->levels < 1 || p->levels > FC_MAX_LEVELS ? "levels must be 1..5" : nullptr,
+                             bad_model(p->mode, 0, p->sense16), bad_reserved(p->reserved),
+                             misaligned({grids_dev, prev_dev, heard_dev, stacks_dev}, {}), bad_steps(p->dx, p->dy)});
+    for (int d = 0; !bad && d < FC_MAX_LEVELS; d++)
+        if (p->moves[d] < 0 || p->moves[d] > PLAN_MAX_STRIDE || (d >= p->levels && p->moves[d] != 0))
+            bad = "moves must be 0..8, and 0 beyond `levels`";
+    if (!bad && (long long)B * p->n_agents > 0x7fffffffLL) bad = "B * n_agents must fit a launch grid";
+    if (bad) return fail(__func__, bad);
+    const int cells = p->side * p->side;
+    LocalForecastArgs a{};
+    a.f.b = belief_args(CoverageArgs{}, p->mode, p->sense16, p->dx, p->dy);
+    a.f.b.c.n = p->n_agents;
+    a.f.b.c.side = p->side;
+    a.f.grid = grids_dev;
+    a.f.pos = prev_dev;
+    a.f.stack = stacks_dev;
+    a.f.levels = p->levels;
+    for (int d = 0; d < FC_MAX_LEVELS; d++) a.f.moves[d] = p->moves[d];
+    // rows are cells (levels * cells) words apart, for every agent of every env: all of them are aligned when the base is and cells % 4 == 0
+    a.f.vec_in = vec4_ok(cells, grids_dev);
+    a.f.vec_out = vec4_ok(cells, stacks_dev);
+    a.heard = heard_dev;
+    hipLaunchKernelGGL(k_local_belief_forecast, dim3((unsigned)B * (unsigned)p->n_agents), dim3(COV_THREADS), 0, (hipStream_t)stream, a);
+    return launched(__func__);
+}
+
+int cs_local_plan_forecast_actions(const cs_local_plan_params *p, const float *state_dev, int B, const int32_t *stacks_dev,
+                                   int64_t *actions_dev, int64_t *plans_dev, int64_t *scores_dev, void *stream) {
+    if (!p || !state_dev || !stacks_dev || !actions_dev || !plans_dev || !scores_dev) return fail(__func__, "a NULL pointer");
+    const char *bad = first({B < 1 ? "B must be >= 1" : nullptr, bad_team(p->n_agents, p->side, p->view_range),
+                             bad_plan(p->depth, p->stride, p->discount), bad_width(p->state_width, p->n_agents),
+                             p->comm_range < -1 || p->comm_range > LOC_MAX_COMM ? "comm_range must be -1 (unlimited) or 0..128" : nullptr,
+                             bad_reserved(p->reserved), misaligned({stacks_dev, state_dev}, {actions_dev, plans_dev, scores_dev})});
+    if (bad) return fail(__func__, bad);
+    const int cells = p->side * p->side, level_words = (cells + 3) & ~3;
+    int seqs = 1;
+    for (int d = 0; d < p->depth; d++) seqs *= 3;
+    // an agent's levels are depth * cells words apart, for every agent of every env: all of them are aligned when the base is and cells % 4 == 0
+    const LocalPlanArgs a{PlanArgs{state_dev, stacks_dev, actions_dev, plans_dev, scores_dev, p->n_agents, p->side, p->state_width,
+                                   16 * p->view_range, p->depth, p->stride, p->discount, (3 * seqs - 3) / 2, seqs, vec4_ok(cells, stacks_dev)},
+                          p->comm_range < 0 ? -1LL : (long long)(16 * p->comm_range) * (long long)(16 * p->comm_range)};
+    const size_t lds = lfc_plan_lds_bytes(p->depth, level_words);
+    // more than 64 KB of dynamic LDS (side 64 with depth 4 or 5) is granted only to a kernel that asked for it
+    if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void *>(&k_local_plan_forecast_actions),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        (void)hipGetLastError();
+        snprintf(g_eerr, sizeof(g_eerr), "%s: the device does not grant %zu bytes of LDS", __func__, lds);
+        return CS_E_LAUNCH;
+    }
+    hipLaunchKernelGGL(k_local_plan_forecast_actions, dim3((unsigned)B), dim3(COV_THREADS), lds, (hipStream_t)stream, a, level_words);
+    return launched(__func__);
 }
 
 int cs_label_episodes(const cs_label_params *p, const float *s_dev, int E, int T, const int32_t *lens_dev, int64_t *labels_dev,

@@ -922,6 +922,66 @@ void belief_forecast(const Tensor &grid, const Tensor &pos, Tensor stack, int64_
     TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
 }
 
+// ---- every agent's private density along the planning horizon (cs_local_belief_forecast): grids [B, n, side * side] int32 (in), prev
+// [B, 8, 2] int32 (in), heard [B, 8] int32 (in), stacks [B, n, L, side * side] int32 (out), L = moves.size().
+void local_belief_forecast(const Tensor &grids, const Tensor &prev, const Tensor &heard, Tensor stacks, int64_t n_agents, int64_t side,
+                           int64_t mode, int64_t sense16, at::IntArrayRef dx, at::IntArrayRef dy, at::IntArrayRef moves) {
+    const char *op = "local_belief_forecast";
+    check_team(op, n_agents, side, 0);
+    check_model(op, mode, sense16);
+    check_steps(op, dx, dy);
+    TORCH_CHECK(moves.size() >= 1 && moves.size() <= 5, "coopsearch: local_belief_forecast: moves must hold 1..5 integers, got ", moves.size());
+    const int64_t L = (int64_t)moves.size();
+    for (int64_t d = 0; d < L; d++)
+        TORCH_CHECK(moves[d] >= 0 && moves[d] <= 8, "coopsearch: local_belief_forecast: moves must be 0..8, got ", moves[d], " at ", d);
+    TORCH_CHECK(grids.dim() == 3 && grids.size(0) >= 1 && grids.size(0) * n_agents <= INT32_MAX && grids.size(1) == n_agents &&
+                    grids.size(2) == side * side,
+                "coopsearch: local_belief_forecast: grids must be [B, ", n_agents, ", ", side * side, "] with B >= 1");
+    const int64_t B = grids.size(0);
+    check_shape(op, prev, "prev", {B, CS_MAX_AGENTS, 2});
+    check_shape(op, heard, "heard", {B, CS_MAX_AGENTS});
+    check_shape(op, stacks, "stacks", {B, n_agents, L, side * side});
+    TORCH_CHECK(grids.is_cuda(), "coopsearch: local_belief_forecast: grids must be a GPU tensor");
+    check_dev(grids, "grids", at::kInt, B * n_agents * side * side, grids);
+    check_dev(prev, "prev", at::kInt, B * CS_MAX_AGENTS * 2, grids);
+    check_dev(heard, "heard", at::kInt, B * CS_MAX_AGENTS, grids);
+    check_dev(stacks, "stacks", at::kInt, B * n_agents * L * side * side, grids);
+    cs_forecast_params p{(int32_t)n_agents, (int32_t)side, (int32_t)L, (int32_t)mode, (int32_t)sense16};   // dx, dy, moves, reserved: 0
+    copy_steps(p, dx, dy);
+    for (int64_t d = 0; d < L; d++) p.moves[d] = (int32_t)moves[d];
+    const int rc = cs_local_belief_forecast(&p, grids.data_ptr<int32_t>(), prev.data_ptr<int32_t>(), heard.data_ptr<int32_t>(), (int)B,
+                                            stacks.data_ptr<int32_t>(), stream_of(grids));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
+// ---- the planner on private forecasts under a communication range (cs_local_plan_forecast_actions): state [B, S >= 4n] float32, stacks
+// [B, n, depth, side * side] int32 (in), actions, plans and scores [B, n] int64 (out); comm_range -1 = unlimited.
+void local_plan_forecast_actions(const Tensor &state, const Tensor &stacks, Tensor actions, Tensor plans, Tensor scores, int64_t n_agents,
+                                 int64_t side, int64_t view_range, int64_t depth, int64_t stride, int64_t discount, int64_t comm_range) {
+    const char *op = "local_plan_forecast_actions";
+    check_team(op, n_agents, side, view_range);
+    check_range(op, "depth", depth, 1, 5);
+    check_range(op, "stride", stride, 1, 8);
+    check_range(op, "discount", discount, 0, 256);
+    TORCH_CHECK(comm_range >= -1 && comm_range <= 128,
+                "coopsearch: local_plan_forecast_actions: comm_range must be -1 (unlimited) or 0..128, got ", comm_range);
+    const auto [B, S] = check_rows(op, state, n_agents);
+    check_shape(op, stacks, "stacks", {B, n_agents, depth, side * side});
+    check_shape(op, actions, "actions", {B, n_agents});
+    check_shape(op, plans, "plans", {B, n_agents});
+    check_shape(op, scores, "scores", {B, n_agents});
+    check_lead(op, state, "state", B * S);
+    check_dev(stacks, "stacks", at::kInt, B * n_agents * depth * side * side, state);
+    check_dev(actions, "actions", at::kLong, B * n_agents, state);
+    check_dev(plans, "plans", at::kLong, B * n_agents, state);
+    check_dev(scores, "scores", at::kLong, B * n_agents, state);
+    const cs_local_plan_params p{(int32_t)n_agents, (int32_t)side, (int32_t)view_range, (int32_t)depth, (int32_t)stride, (int32_t)discount,
+                                 (int32_t)S, (int32_t)comm_range, 0};
+    const int rc = cs_local_plan_forecast_actions(&p, state.data_ptr<float>(), (int)B, stacks.data_ptr<int32_t>(), actions.data_ptr<int64_t>(),
+                                                  plans.data_ptr<int64_t>(), scores.data_ptr<int64_t>(), stream_of(state));
+    TORCH_CHECK(rc == CS_OK, cs_episodes_last_error());
+}
+
 int64_t abi_version() { return cs_abi_version(); }
 
 // ---- QMIX learner: the GRU recurrence over T steps (cs_gru_seq_forward / cs_gru_seq_backward) ------------------------------
@@ -1268,6 +1328,11 @@ TORCH_LIBRARY(coopsearch, m) {
           "int[] moves) -> ()", &belief_forecast);
     m.def("plan_forecast_actions(Tensor state, Tensor stack, Tensor(a!) actions, Tensor(b!) plans, Tensor(c!) scores, int n_agents, "
           "int side, int view_range, int depth, int stride, int discount) -> ()", &plan_forecast_actions);
+    m.def("local_belief_forecast(Tensor grids, Tensor prev, Tensor heard, Tensor(a!) stacks, int n_agents, int side, int mode, "
+          "int sense16, int[] dx, int[] dy, int[] moves) -> ()", &local_belief_forecast);
+    m.def("local_plan_forecast_actions(Tensor state, Tensor stacks, Tensor(a!) actions, Tensor(b!) plans, Tensor(c!) scores, "
+          "int n_agents, int side, int view_range, int depth, int stride, int discount, int comm_range) -> ()",
+          &local_plan_forecast_actions);
     m.def("sweep_episodes(Tensor states, Tensor counts, Tensor(a!) first, Tensor(b!) new_cells, Tensor(c!) seen_cells, int n_agents, "
           "int side, int view_range) -> ()", &sweep_episodes);
     m.def("move_targets(Tensor cfg, Tensor(a!) blob, int mode, int persist, int seed, float speed, float sense, int env_offset) -> ()",

@@ -45,7 +45,8 @@ extern "C" {
                               then cs_label_params, cs_label_episodes and cs_bc_loss, then cs_grid_params, cs_grid_features and
                               cs_feature_episodes, then cs_local_params and cs_local_coverage_actions, then cs_local_belief_params and
                               cs_local_belief_actions, then cs_local_label_params, cs_local_grid_features and cs_local_feature_episodes,
-                              then cs_local_plan_params and cs_local_plan_actions
+                              then cs_local_plan_params and cs_local_plan_actions, then cs_local_belief_forecast and
+                              cs_local_plan_forecast_actions
                               (no existing export or struct changed: a version-7 caller works unchanged) */
 #define CS_MAX_AGENTS 8
 #define CS_MAX_TARGETS 16
@@ -897,6 +898,29 @@ typedef struct cs_local_plan_params {
  * cs_episodes_last_error()'s. */
 int cs_local_plan_actions(const cs_local_plan_params *p, const float *state_dev, int B, const int32_t *grids_dev, int64_t *actions_dev,
                           int64_t *plans_dev, int64_t *scores_dev, void *stream);
+
+/* ---- the forecast planner on PRIVATE grids under a communication range ------------------------------------
+ * cs_belief_forecast predicts ONE grid per env with every agent held in place.  cs_local_belief_forecast predicts agent i's own grid,
+ * grids[b][i], with the agents of heard[b][i] alone held at their prev positions: the word is read as cs_local_belief_actions reads
+ * it ((heard & ((1 << n_agents) - 1)) | (1 << i)), the heard agents are listed in index order, and levels, moves, the clamp and the
+ * cap are cs_belief_forecast's.  After a cs_local_belief_actions call prev holds the current positions and heard the links of that
+ * call.  In walk mode the mask plays no part.  cs_local_plan_forecast_actions is cs_local_plan_actions with `depth` levels per agent:
+ * the gain of a segment end point d is summed over level d of agent i's stack, and the claims of the linked agents j < i are zeroed in
+ * every level.  DEFINED by local_forecast.local_forecast_torch and local_forecast.local_plan_forecast_actions_torch (stock torch ops,
+ * integer after one quantisation); the kernels reproduce them bit for bit.  Both reuse an existing params struct.
+ *   grids_dev   int32 [B][n_agents][side * side], in      prev_dev  int32 [B][8][2], in      heard_dev  int32 [B][8], in
+ *   stacks_dev  int32 [B][n_agents][levels][side * side], out of cs_local_belief_forecast, in (READ ONLY) of
+ *   cs_local_plan_forecast_actions, whose `depth` is the number of levels; state_dev, actions_dev, plans_dev, scores_dev as
+ *   cs_local_plan_actions'
+ * One launch each on `stream`: cs_local_belief_forecast one workgroup per (env, agent) with atomics on LDS only (integer: the result
+ * does not depend on their order), cs_local_plan_forecast_actions one workgroup per env with 3.5 KB + 4 depth side^2 bytes of LDS
+ * (85.4 KB at side 64 and depth 5; CS_E_LAUNCH if the device does not grant it).  No synchronisation.  CS_E_CONFIG (before any
+ * launch) for a field out of range, a non-zero `reserved`, a NULL or misaligned pointer or B < 1.  The message is
+ * cs_episodes_last_error()'s. */
+int cs_local_belief_forecast(const cs_forecast_params *p, const int32_t *grids_dev, const int32_t *prev_dev, const int32_t *heard_dev,
+                             int B, int32_t *stacks_dev, void *stream);
+int cs_local_plan_forecast_actions(const cs_local_plan_params *p, const float *state_dev, int B, const int32_t *stacks_dev,
+                                   int64_t *actions_dev, int64_t *plans_dev, int64_t *scores_dev, void *stream);
 
 /* ---- QMIX learner: the GRU recurrence of the agent network over T steps, forward and backward ---------------------
  * Replaces the per-transition unroll of policy/qmix.py:160-182 (get_q_values) over network/base_net.py:40-46
